@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the linearization hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs and nothing else: set up, settle, W warm-up steps, the
+K timed steps, the result line (metric, value, unit, higher_is_better, dtype, ms_per_step, the timing
+block and what the library counted over the timed region).  --dump-outputs DIR writes what the last
+timed step handed its caller — the combined H (6x6), b (6) and cost — as DIR/H.npy, DIR/b.npy and
+DIR/cost.npy (float64, or float32 where the path returns that); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.  Everything else described below — the kernel-time
+pass and the roofline figures that rest on it, check.vs_oracle, configs, cpu_baseline, and for N > 1
+the RCCL pass, the other transports and the strong-scaling split — is measured only with --full.
 
 A *step* is one LM linearization sweep as the optimizer sees it: for the current parameter
 vector x, every rank runs the point-to-point analytic linearize kernels over its resident shard,
@@ -20,7 +29,7 @@ children, before anything touches the GPU) and relays rank 0's line; under torch
 Timed region: settle | W warm-up steps | barrier + torch.cuda.synchronize() | t0 | K blocking steps |
 barrier + synchronize | t1.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0 (contract in the task statement) including, with --full,
   timing       — the K individual step times of rank 0 (per_step_us, median, min, first)
   check.vs_oracle — one GPU linearize over rank 0's shard against the CPU restatement's H, b, cost
                  on the same correspondences (the sums the cpu_baseline sweeps compute anyway), bar 1e-6
@@ -75,6 +84,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything else the line can carry: kernel "
+                         "times and roofline figures, the oracle check, the configs block, the CPU "
+                         "baseline, and for N>1 the RCCL pass, every other transport and config 4")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (H, b, cost) as DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=10_000_000, help="correspondences PER GPU")
     ap.add_argument("--total-n", type=int, default=0,
                     help="strong scaling: shard this many correspondences over the GPUs "
@@ -125,7 +140,22 @@ def parse_args():
                     default=float(os.environ.get("MOPT_BENCH_DEADLINE_S", "330")),
                     help="N>1: seconds after the ranks have their data by which the run ends "
                          "whatever has or has not finished (watchdog)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline's timed steps only
+        args.no_cpu_baseline = args.no_configs = args.no_compare = True
+        args.hbm_check_n = args.rotating_costs = 0
+    return args
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, order="C"))
 
 
 def make_shard_on_gpu(torch, n, rank, dtype):
@@ -267,14 +297,17 @@ def camera_main(args):
             out = step(k)
         return time.perf_counter() - t0, out
 
-    elapsed_unlinked, _ = timed()
+    elapsed_unlinked = timed()[0] if args.full else None
     # the costs of one problem, as an optimizer holds them: the first one asked at an x queues the
     # other's sweep too (mopt_costs_link); the loop above is unchanged
     mo.capi.link_costs(costs)
     elapsed, (H, b, y) = timed()
     mo.capi.link_costs([])
-    kernel_ms = kernel_pass_ms(args.steps)
-    achieved = n * 40 / (kernel_ms * 1e-3) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"H": H, "b": b, "cost": np.float64(y)})
+    # a plain run takes no kernel-time pass: its roofline block is the timed steps' own rate
+    kernel_ms = kernel_pass_ms(args.steps) if args.full else None
+    achieved = n * 40 / ((kernel_ms if args.full else elapsed / args.steps * 1e3) * 1e-3) / 1e9
     print(json.dumps({
         "metric": "point-correspondences/sec per LM linearization sweep; % HBM peak",
         "value": n * args.steps / elapsed, "unit": "residual-blocks/s", "n_gpus": 1,
@@ -285,9 +318,11 @@ def camera_main(args):
                                "two costs (40k + 60k), Geman-McClure(100), forward differences, "
                                "both linearized and summed per step; the two costs linked "
                                "(mopt_costs_link)"},
-        "ms_per_step_unlinked": elapsed_unlinked / args.steps * 1e3,
+        "ms_per_step_unlinked": elapsed_unlinked / args.steps * 1e3 if args.full else None,
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": None, "kernel_ms": kernel_ms,
+                     "measured_over": "a kernel-time pass of its own" if args.full else
+                     "the timed steps as a whole (kernel times are taken with --full)",
                      "note": "4 MB of input: launch-latency-bound, not bandwidth-bound"},
         "check": {"sum_sq": float(y)}, "cpu_baseline": None}), flush=True)
 
@@ -519,15 +554,22 @@ def main():
     # it (attach_combines); it leaves the cost on MOPT_COMBINE_NONE.
     usable, collective, rccl_note = [], "none", None
     if world > 1:
-        usable = attach_combines(cost, rank, world, want=("host", "peer", "rccl"), log=log)
+        auto = ("host", "peer", "rccl")
+        prefer = auto if args.collective == "auto" else (args.collective,) + tuple(
+            c for c in auto if c != args.collective)
+        if args.full:
+            usable = attach_combines(cost, rank, world, want=auto, log=log)
+        else:
+            # a plain run attaches the headline's transport only: the first in order that every rank could
+            for name in (c for c in prefer if c in auto):
+                usable = attach_combines(cost, rank, world, want=(name,), log=log)
+                if usable:
+                    break
         if "rccl" not in usable:
             rccl_note = ("ranks share GPUs (rehearsal backend %r): RCCL refuses duplicate devices"
                          % backend) if backend != "nccl" else "ncclCommInitRank failed on some rank"
         # a transport asked for by name comes first; one that could not be attached (RCCL between ranks
         # that share a GPU, for one) falls back to the automatic order, and the line says so
-        auto = ("host", "peer", "rccl")
-        prefer = auto if args.collective == "auto" else (args.collective,) + tuple(
-            c for c in auto if c != args.collective)
         collective = next((c for c in prefer if c in usable), "torch")
     modes = {"none": mo.COMBINE_NONE, "rccl": mo.COMBINE_RCCL, "host": mo.COMBINE_HOST,
              "peer": mo.COMBINE_PEER}
@@ -556,6 +598,7 @@ def main():
         return sw, hits, direct
 
     region = {}  # the library's counters over the most recent timed region (timed_pass fills it)
+    last_out = {}  # what the last step of the most recent timed region returned (--dump-outputs)
 
     def timed_pass(the_cost, combine, steps, warmup, settle, via_torch=None, mode=None, step_fn=None,
                    counted=None):
@@ -628,6 +671,8 @@ def main():
             elapsed = float(tmax.item())
         if err is not None:
             raise err
+        last_out.clear()
+        last_out.update({"H": np.array(H), "b": np.array(b), "cost": np.array(s).reshape(())})
         return elapsed, np.array(H, dtype=np.float64), float(s), stamps
 
     def step_times(stamps, elapsed_s=None):
@@ -699,6 +744,8 @@ def main():
         if res is None:
             raise SystemExit("rank %d: no way of adding the ranks' sums worked" % rank)
         elapsed, H, s, stamps = res
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out)
     headline_region = dict(region, what="mopt_cost_stats / mopt_cost_direct_dispatches deltas of the "
                            "headline's cost between t0 and t1 of the timed region: K steps are K sweeps "
                            "launched, none answered from the kept result; direct_dispatches = K when the "
@@ -889,14 +936,18 @@ def main():
 
     progress["stage"] = "kernel-time pass"
     ksteps = args.kernel_steps if args.kernel_steps > 0 else min(args.steps, 100)
-    kernel_ms, launches = kernel_pass(cost, ksteps)
-    # one untimed sweep of this rank's own shard (combine off) at the x the CPU baseline sweeps at:
-    # what check.vs_oracle compares with the oracle's sums
     x_check = ds.X_GENERIC.astype(np_dtype)
-    own_sums = cost.linearize(x_check, jac_mode)
-
     ms_per_step = elapsed / args.steps * 1e3
-    achieved = args.n * bpc / (kernel_ms * 1e-3) / 1e9
+    if args.full:
+        kernel_ms, launches = kernel_pass(cost, ksteps)
+        # one untimed sweep of this rank's own shard (combine off) at the x the CPU baseline sweeps at:
+        # what check.vs_oracle compares with the oracle's sums
+        own_sums = cost.linearize(x_check, jac_mode)
+        achieved = args.n * bpc / (kernel_ms * 1e-3) / 1e9
+    else:
+        # a plain run takes no kernel-time pass: its roofline block is the timed steps' own rate
+        kernel_ms, launches, own_sums = None, 0, None
+        achieved = args.n * bpc / (ms_per_step * 1e-3) / 1e9
     traffic = None
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
     if os.path.exists(tpath):
@@ -967,7 +1018,9 @@ def main():
             "traffic_bytes": traffic["bytes"] if traffic else None,
             "kernel_ms": kernel_ms,
             "kernel_launches_timed": launches,
-            "kernel_timing": "separate pass after the timed steps, same dispatch path as the steps; every "
+            "kernel_timing": "none: the figures of this block are the timed steps' own rate (kernel + "
+                             "finalize + result on the host); kernel times are taken with --full"
+            if not args.full else "separate pass after the timed steps, same dispatch path as the steps; every "
                              "launch carries its own dispatch timestamps (the packet processor's start / "
                              "end of the kernel: the profiling signal of the library's queue, or "
                              "hipExtLaunchKernelGGL on the HIP stream); rank 0's GPU",
@@ -1001,7 +1054,7 @@ def main():
         line["by_collective"] = per
         line["roofline"]["step_frac_by_collective"] = {collective: per[collective]["step_frac"]}
 
-    if world == 1 and args.variant == "auto" and args.mode != "analytic_tst":
+    if args.full and world == 1 and args.variant == "auto" and args.mode != "analytic_tst":
         # the same sweep evaluated literally (every residual and Jacobian entry per point, as the
         # reference does) — a driver-timed number for that kernel too
         cost.set_kernel_variant(mo.KERNEL_LITERAL)
@@ -1020,7 +1073,7 @@ def main():
                  "frac": achieved / HBM_PEAK_GBS,
                  "what": "the headline's own cost swept back to back, as the timed steps run it: includes "
                          "what L2 and the Infinity Cache keep of its input from one sweep to the next"}
-    line["roofline"]["measured_over"] = "one cost, back to back"
+    line["roofline"]["measured_over"] = "one cost, back to back" if args.full else "the timed steps as a whole"
 
     def apply_cache_proof():
         try:
@@ -1049,7 +1102,7 @@ def main():
     # N = 1: here.  N > 1: after the line can stand and the RCCL pass has run (below) — a first run on more
     # than one GPU must not lose its headline or its RCCL figure to an extra, and the watchdog reports the
     # line as it stands (roofline over one cost, `measured_over` saying so) if this pass should stall.
-    if world == 1:
+    if world == 1 and args.full:
         apply_cache_proof()
 
     # ---- the other BASELINE configs that fit one GPU, driver-timed in the same line ------------
@@ -1096,7 +1149,9 @@ def main():
     progress["complete"] = True
 
     # ---- RCCL: part of the measurement proper, whatever the headline transport ------------------
-    if world > 1:
+    if world > 1 and not args.full and collective == "rccl":
+        line["value_rccl"] = per["rccl"]["value"]
+    if world > 1 and args.full:
         progress["stage"] = "RCCL pass"
         info = {"attached": "rccl" in usable}
         if "rccl" in usable:
@@ -1133,7 +1188,7 @@ def main():
         line["rccl"] = info
         line["config"]["rccl_ranks"] = info.get("ranks")
 
-    if world > 1:
+    if world > 1 and args.full:
         progress["stage"] = "rotating costs (HBM-only kernel time)"
         apply_cache_proof()
         barrier()  # (the passes below hold collectives again: every rank starts them together)

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out/cama
 for rep in 1 2; do
 for v in "$@"; do
   export MOPT_LIBRARY=$GRAFT_REPO_ROOT/build/ab/lib_$v.so
-  python3 bench.py --workload camera --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v rep=$rep camera step ms_per_step %.5f kernel_ms %.5f' % (j['ms_per_step'], j['roofline']['kernel_ms']))"
+  python3 bench.py --workload camera --full --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v rep=$rep camera step ms_per_step %.5f kernel_ms %.5f' % (j['ms_per_step'], j['roofline']['kernel_ms']))"
   python3 scripts/camera_lm_timing.py 2>&1 | grep -v amdgpu.ids | tail -3 | sed "s/^/$v rep=$rep /"
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/camab/${v}_$rep -o k -- python3 scripts/camera_lm_timing.py > /dev/null 2>&1
   rm -f gpurun_out/camab/${v}_$rep/k_kernel_trace.csv

@@ -4,7 +4,7 @@
 out=gpurun_out/r2q
 mkdir -p $out
 for n in 10000000 5000000 2500000 1250000; do
-  python3 bench.py --n $n --steps 500 --warmup 50 --no-cpu-baseline > $out/single_$n.json 2> $out/single_$n.err
+  python3 bench.py --n $n --steps 500 --warmup 50 --full --no-cpu-baseline > $out/single_$n.json 2> $out/single_$n.err
   python3 - "$out/single_$n.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -3,7 +3,7 @@
 mkdir -p gpurun_out/r5
 for rep in 1 2 3; do
   for every in 1000000000 32; do for pause in 0 2; do
-    MOPT_MARKER_EVERY=$every python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 1 --pause-after-sync-ms $pause 2>/dev/null \
+    MOPT_MARKER_EVERY=$every python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --cpu-seconds 1 --pause-after-sync-ms $pause 2>/dev/null \
       > gpurun_out/r5/mb_${every}_${pause}_$rep.json
     python3 - "$every" "$rep" "$pause" <<'PY'
 import json, sys

@@ -4,7 +4,7 @@
 # (MOPT_STREAMING_LOADS: 0 = the library's choice — non-temporal past 32 MiB —, 1 never, 2 always)
 for n in 500000 1000000 2000000 3000000 4000000 5000000; do
   for s in 0 1 2; do
-    line=$(MOPT_STREAMING_LOADS=$s python3 bench.py --n $n --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | tail -1)
+    line=$(MOPT_STREAMING_LOADS=$s python3 bench.py --n $n --steps 200 --warmup 20 --full --no-cpu-baseline 2>/dev/null | tail -1)
     python3 - "$n" "$s" "$line" <<'PY'
 import sys, json
 n, s, line = sys.argv[1], sys.argv[2], sys.argv[3]

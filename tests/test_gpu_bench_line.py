@@ -14,10 +14,50 @@ from tests import datasets as ds
 pytestmark = pytest.mark.gpu
 
 
+def test_plain_run_times_its_steps_only_and_dumps_what_they_returned(hip_lib, tmp_path):
+    """Without --full the line is the headline's and nothing else (no kernel-time pass, oracle check,
+    configs or CPU baseline), --steps is the number of timed steps, and --dump-outputs writes the H, b
+    and cost of the last timed step: the same sums a caller gets from the library over the same seeded
+    inputs at that step's x.  Bar: both are fp64 sums of n = 300 000 terms taken in an order that may
+    differ (atomics), so they differ by at most n * 2^-53 = 3.3e-11 of the sum of magnitudes; 1e-10
+    norm-wise."""
+    import torch
+
+    import bench
+    n, steps = 300_000, 7
+    out = subprocess.run([sys.executable, os.path.join(ds.ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", "3", "--n", str(n), "--settle-ms", "0", "--dump-outputs", str(tmp_path)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["warmup"] == 3 and line["n_gpus"] == 1
+    assert line["unit"] == "correspondences/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0 and abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert len(line["timing"]["per_step_us"]) == steps
+    reg = line["check"]["timed_region"]
+    assert reg["steps"] == steps and reg["sweeps"] == steps and reg["cache_hits"] == 0, reg
+    assert "configs" not in line and line["cpu_baseline"] is None and "vs_oracle" not in line["check"]
+    assert line["roofline"]["kernel_ms"] is None and "literal_kernel_ms" not in line["roofline"]
+    assert sorted(os.listdir(tmp_path)) == ["H.npy", "b.npy", "cost.npy"]
+    H, b, c = (np.load(os.path.join(tmp_path, name + ".npy")) for name in ("H", "b", "cost"))
+    assert H.shape == (6, 6) and b.shape == (6,) and c.shape == () and H.dtype == b.dtype == c.dtype == np.float64
+    assert float(c) == line["check"]["sum_sq"] and H[0, 0] == line["check"]["H00"] == float(n)
+    src, tgt = bench.make_shard_on_gpu(torch, n, 0, torch.float64)
+    torch.cuda.synchronize()
+    cost = hip_lib.Point2PointCost(src.data_ptr(), tgt.data_ptr(), device=0, dtype=np.float64,
+                                   device_ptrs=True, count=n)
+    Hw, bw, cw = cost.linearize(ds.X_GENERIC + 1e-4 * ((steps - 1) % 16), hip_lib.JAC_ANALYTIC)
+    cost.close()
+    assert np.abs(H - Hw).max() <= 1e-10 * np.abs(Hw).max()
+    assert np.abs(b - bw).max() <= 1e-10 * np.abs(bw).max() and abs(float(c) - cw) <= 1e-10 * cw
+
+
 def test_single_gpu_line_carries_every_object(hip_lib):
     out = subprocess.run([sys.executable, os.path.join(ds.ROOT, "bench.py"), "--gpus", "1", "--steps", "20",
                           "--warmup", "5", "--n", "1000000", "--cpu-seconds", "1", "--hbm-check-n", "3000000",
-                          "--rotating-costs", "3"],
+                          "--rotating-costs", "3", "--full"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]

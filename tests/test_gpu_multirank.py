@@ -302,7 +302,7 @@ def test_bench_launches_its_own_ranks(hip_lib):
         env["MOPT_BENCH_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ds.ROOT, "bench.py"), "--gpus", "2",
                           "--steps", "20", "--warmup", "3", "--n", "300000", "--settle-ms", "5",
-                          "--cpu-seconds", "1"],
+                          "--cpu-seconds", "1", "--full"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
@@ -310,6 +310,36 @@ def test_bench_launches_its_own_ranks(hip_lib):
     line = json.loads(lines[0])
     assert line["check"]["H00"] == 600000.0  # both shards were summed
     _check_multirank_line(line, 2, rehearsal)
+
+
+def test_plain_bench_run_with_two_ranks_attaches_the_headline_transport_only(hip_lib, tmp_path):
+    """Without --full a > 1-rank run attaches one transport (the first in order that every rank could),
+    times the K steps over it and stops: no RCCL pass, no comparison passes, no config 4, no CPU
+    baseline — and --dump-outputs holds the sums over both shards."""
+    import json
+    import torch
+    env = dict(os.environ)
+    if torch.cuda.device_count() < 2:
+        env["MOPT_BENCH_BACKEND"] = "gloo"
+    out = subprocess.run([sys.executable, os.path.join(ds.ROOT, "bench.py"), "--gpus", "2",
+                          "--steps", "10", "--warmup", "3", "--n", "300000", "--settle-ms", "5",
+                          "--dump-outputs", str(tmp_path)],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert out.returncode == 0, out.stderr.decode()[-3000:]
+    lines = [ln for ln in out.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    cfg = line["config"]
+    assert line["n_gpus"] == 2 and line["steps"] == 10 and line["ms_per_step"] > 0
+    assert cfg["collective"] in ("host", "peer", "rccl") and cfg["collectives_attached"] == [cfg["collective"]]
+    assert set(line["by_collective"]) == {cfg["collective"]} and line["check"]["H00"] == 600000.0
+    assert line["check"]["timed_region"]["sweeps"] == 10
+    for moved in ("rccl", "config4_strong", "ms_per_step_by_collective", "configs"):
+        assert moved not in line, moved
+    assert line["cpu_baseline"] is None and line["extras_incomplete"] is False
+    H = np.load(os.path.join(tmp_path, "H.npy"))
+    assert H.shape == (6, 6) and H[0, 0] == 600000.0
+    assert float(np.load(os.path.join(tmp_path, "cost.npy"))) == line["check"]["sum_sq"]
 
 
 def test_eight_rank_processes_on_one_gpu_are_refused_by_name(hip_lib):
@@ -371,7 +401,7 @@ def test_driver_command_rehearsed_with_four_ranks(hip_lib):
                           "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                           "--master-port", str(port), os.path.join(ds.ROOT, "bench.py"),
                           "--gpus", str(world), "--steps", "20", "--warmup", "5",
-                          "--collective", "rccl"],
+                          "--collective", "rccl", "--full"],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=500)
     elapsed = time.time() - t0
     assert out.returncode == 0, out.stderr.decode()[-3000:]
