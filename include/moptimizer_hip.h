@@ -104,22 +104,25 @@ enum mopt_create_flags {
 /* How a sweep evaluates the reference's per-residual arithmetic. */
 enum mopt_kernel_variant {
   MOPT_KERNEL_AUTO = 0,    /* fastest variant that meets the parity bar (1e-6 on H, b, cost) for
-                              the mode: moments, except forward differences at an x with some
-                              0 < |x_j| < 0.08 (literal) — in the blocking and asynchronous
-                              calls AND, since round 6, at every point the device-resident loop
-                              (mopt_lm_minimize) evaluates: its sweep and finalize kernels hold
-                              both forward-difference forms and the step kernel, which forms
-                              the next x, names the one the rule asks for there
+                              the mode: moments, except where the scene's scale takes them off
+                              the bar — forward differences at an x with a small step, and the
+                              left-perturbation Jacobian of a far source mapped near the origin
+                              (both rules, with their thresholds: the paragraph at
+                              mopt_cost_set_kernel_variant) — which are evaluated literally, in
+                              the blocking and asynchronous calls AND in the device-resident
+                              loop (mopt_lm_minimize): its forward-difference sweep and finalize
+                              kernels hold both forms and the step kernel, which forms the next
+                              x, names the one the rule asks for there
                               (mopt_cost_lm_choice_stats counts them); so does the one-launch
                               solve of small problems                                          */
   MOPT_KERNEL_LITERAL = 1, /* every residual and Jacobian entry formed per point, then
                               w * J^T * S * J accumulated entry by entry, as the reference does */
   MOPT_KERNEL_MOMENTS = 2, /* Jacobians that are affine in the source point (all point2point
-                              modes) reduced through weighted point/residual moments — except
-                              for forward differences with some 0 < |x_j| < 0.08, where that
-                              evaluation leaves the 1e-6 bar (it lacks the reference's own
-                              per-point cancellation noise eps |R p + t| / h_j) and the literal
-                              evaluation is used: in every call and at every point of the
+                              modes) reduced through weighted point/residual moments — with the
+                              two exceptions of AUTO, at the same thresholds, where that
+                              evaluation leaves the 1e-6 bar (forward differences: it lacks the
+                              reference's own per-point cancellation noise eps |R p + t| / h_j)
+                              and the literal evaluation is used: in every call and in the
                               device-resident loop, as under AUTO                              */
   MOPT_KERNEL_MOMENTS_ALWAYS = 3 /* moments whatever the step size: for measurements; forward
                               differences then differ from the reference's by up to
@@ -269,6 +272,26 @@ MOPT_API int mopt_cost_destroy(mopt_cost *cost);
 
 MOPT_API int mopt_cost_set_covariance(mopt_cost *cost, const void *cov_colmajor);
 MOPT_API int mopt_cost_set_loss(mopt_cost *cost, int loss_kind, double parameter);
+/* The numerical domain the 1e-6 bar is tested over (tests/test_gpu_scene_scale.py): clouds at the
+ * sensor (U[0,10]^3), in a site frame (1e3 m from the origin) and a map frame (1e5 m), a UTM scan
+ * (1e6 and 7e6 m) registered to a local target, a local scan registered into a map frame (|t| = 1e6),
+ * a millimetre-sized object and a flat wall; H judged after the scaling x_i -> x_i / sqrt(H_ii) under
+ * which Levenberg-Marquardt's H + lambda diag(H) is invariant, against 80-bit sums.  The sources'
+ * bounding sphere (centre c0, radius r) is taken on the device when the data is laid out.  Outside the
+ * small-scene regime AUTO and MOMENTS leave the moments where they would leave that bar:
+ *  - MOPT_JAC_ANALYTIC_LEFT is evaluated literally, per point, when |t|^2 > 1e3 rho_w^2,
+ *    rho_w = |R c0 + t| + r a bound of |R p + t| (the basis about p = 0 cancels N |t|^2 down to
+ *    N |R p + t|^2 when a far source is mapped near the origin).  The device-resident loop decides once
+ *    per solve: literally throughout where some pose could meet that rule, |c0|^2 > 1e3 r^2 (a cloud far
+ *    from the origin of its own frame); every other cost keeps the moments and, if small, the one-launch
+ *    solve.
+ *  - forward differences are evaluated literally where some |x_j| < 0.08 max(1, rho / 30),
+ *    rho = |c0| + r + |t| a bound of |R p + t|, x_j = 0 counting as 1 (its step is sqrt(eps)): the
+ *    reference's cancellation noise eps rho / h_j is part of its answer there.  0.08 is the threshold
+ *    measured at rho <= 30; the rule holds in the blocking and asynchronous calls and at every point of
+ *    the device-resident loop.  There one gate serves all costs of a problem and takes the largest |c0| + r
+ *    among them: with several costs it may choose the literal form where the blocking call of the smaller
+ *    cloud would still take the moments, never the other way round. */
 MOPT_API int mopt_cost_set_kernel_variant(mopt_cost *cost, int variant);
 
 /* count, n (parameters), m (outputs per residual), scalar_bytes, device; any pointer may be NULL */
@@ -435,7 +458,10 @@ MOPT_API int mopt_cost_get_combine(const mopt_cost *cost, int *combine_mode, int
  * that keeps the correspondences in registers and never leaves the kernel between points (same sums,
  * added in another order; MOPT_LM_ONE_LAUNCH_TILES=0 in the environment keeps the launch-per-point
  * form; `window` does not apply); where the forward-difference form is chosen per point
- * (MOPT_KERNEL_AUTO / _MOMENTS with MOPT_JAC_NUMERIC) that kernel holds both forms.
+ * (MOPT_KERNEL_AUTO / _MOMENTS with MOPT_JAC_NUMERIC) that kernel holds both forms.  It sweeps by
+ * moments only: a cost evaluated literally for the whole solve (MOPT_KERNEL_LITERAL, or
+ * MOPT_JAC_ANALYTIC_LEFT over a cloud far from its frame's origin, |c0|^2 > 1e3 r^2, see
+ * mopt_cost_set_kernel_variant) takes the launch-per-point form whatever its size.
  *
  * costs / jacobian_modes: the costs of Optimizer::addCost (optimizer.h:58) with the Jacobian mode
  * of each (the cost class the caller would have used), at most 4, same device / scalar type / n;

@@ -282,13 +282,51 @@ void fillBasis(const mopt_cost *c, int jac_mode, const mopt::P2PSweepArgs<S> &a,
 // 2e-8 / |x_j| (tests/tools/parity_table.py; the literal sweep matches the reference to 1e-14 at every
 // step size).  So below |x_j| = 0.08, where 4 x that measurement would pass the 1e-6 bar, AUTO
 // evaluates literally; x_j = 0 takes the fixed step sqrt(eps) and is fine.
+// That measurement was taken on clouds with rho = |R p + t| = 10..30.  The distance is the
+// reference's cancellation noise eps rho / h_j, linear in rho: the threshold is 0.08 rho / 30 beyond
+// rho = 30 and stays 0.08 below (mopt::forwardStepThreshold), with rho = (the bound of |p| stored when
+// the data was laid out) + |t|, a bound of |R p + t| that costs nothing per call.  At a large rho the
+// fixed step of x_j = 0 is no longer fine either: sqrt(eps) is the step of |x_j| = 1 and is judged
+// as that.  Same rule in the step kernel of the device-resident loop (lm_device.hpp).
 template <typename S>
-bool hasSmallForwardStep(const S *x) {
+bool hasSmallForwardStep(const mopt_cost *c, const S *x) {
+  const double t_norm = std::sqrt(double(x[0]) * double(x[0]) + double(x[1]) * double(x[1]) +
+                                  double(x[2]) * double(x[2]));
+  const double threshold = mopt::forwardStepThreshold(c->src_bound + t_norm);
   for (int j = 0; j < kNumParams; ++j) {
     const double a = std::fabs(double(x[j]));
-    if (a > 0.0 && a < 0.08) return true;
+    if ((a > 0.0 ? a : 1.0) < threshold) return true;
   }
   return false;
+}
+
+// AUTO's and MOMENTS' choice for the analytic modes: the moments, except where the left-perturbation
+// Jacobian [I | -skew(R p + t)] would cancel.  Its affine basis about p = 0 is J0 = -skew(t),
+// J_k = -skew(R e_k): where the pose brings a far source near the origin (a map-frame scan registered
+// to a local target, t ~ -R c) terms of N |t|^2 cancel down to N |R p + t|^2 and H keeps
+// eps |t|^2 / |R p + t|^2 of error (profiles/NOTES.md "Scene scale").  Literal, per point, when
+// |t|^2 > 1e3 rho_w^2, rho_w = |R c0 + t| + r bounding |R p + t| from the sources' stored bounding
+// sphere (c0, r): at most 1e3 eps = 2e-13 is then lost to the moments.  MOMENTS_ALWAYS keeps the
+// moments to measure.
+bool leftBasisCancels(const mopt_cost *c, const double R[9], const double t[3]) {
+  double w2 = 0.0, t2 = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    const double w = R[r * 3] * c->src_center[0] + R[r * 3 + 1] * c->src_center[1] +
+                     R[r * 3 + 2] * c->src_center[2] + t[r];
+    w2 += w * w;
+    t2 += t[r] * t[r];
+  }
+  const double rho_w = std::sqrt(w2) + c->src_radius;
+  return t2 > 1e3 * rho_w * rho_w;
+}
+// The device-resident loop chooses once per solve, for every pose it may reach: |t| <= |w| + |c0| with
+// w = R c0 + t, so the rule above can only fire where |c0| > sqrt(1e3) r, whatever the pose.  Such a
+// cost (a cloud far from the origin of its own frame) is swept literally throughout the solve; every
+// other keeps the moments, and a small one the one-launch solve.
+bool leftBasisMayCancel(const mopt_cost *c) {
+  const double c2 = c->src_center[0] * c->src_center[0] + c->src_center[1] * c->src_center[1] +
+                    c->src_center[2] * c->src_center[2];
+  return c2 > 1e3 * c->src_radius * c->src_radius;
 }
 
 template <typename S>
@@ -296,11 +334,18 @@ int p2pLinearizeAsync(mopt_cost *c, int jac_mode, const S *x, double *d_result, 
                       const mopt::HostPublish &pub) {
   mopt::P2PSweepArgs<S> args;
   fillP2PArgs<S>(c, x, jac_mode == MOPT_JAC_NUMERIC, args);
-  bool moments;
-  switch (c->variant) {
-    case MOPT_KERNEL_LITERAL: moments = false; break;
-    case MOPT_KERNEL_MOMENTS_ALWAYS: moments = true; break;
-    default: moments = !(jac_mode == MOPT_JAC_NUMERIC && hasSmallForwardStep<S>(x)); break;
+  bool moments = c->variant != MOPT_KERNEL_LITERAL;
+  if (moments && c->variant != MOPT_KERNEL_MOMENTS_ALWAYS) {
+    if (jac_mode == MOPT_JAC_NUMERIC) {
+      moments = !hasSmallForwardStep<S>(c, x);
+    } else if (jac_mode == MOPT_JAC_ANALYTIC_LEFT) {
+      double R[9], t[3];
+      for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) R[r * 3 + k] = double(args.T[0][r * 4 + k]);
+        t[r] = double(args.T[0][r * 4 + 3]);
+      }
+      moments = !leftBasisCancels(c, R, t);
+    }
   }
   if (moments) {
     mopt::AffineBasis basis;
@@ -937,9 +982,13 @@ int residentPrepareP2P(mopt_cost *c, int jac_mode, bool moments, double *partial
 // in round 5 at 21.5 against 17.9 us per evaluated point at 1 M, 101.6 against 84.4 at 10 M; the choice per
 // point pays that only at the points that need it (and 0.6-2 us per point for the kernels that hold both
 // forms: profiles/r6_device_loop_choice.txt).
+// ... and the left-perturbation Jacobian of a cloud far from its frame's origin, which some pose of
+// the solve may map near the origin (leftBasisMayCancel: the device writes the same basis about p = 0,
+// lm_device.hpp writeSweepConstants).
 bool usesMoments(const mopt_cost *c, int jac_mode) {
-  (void)jac_mode;
-  return c->variant != MOPT_KERNEL_LITERAL;
+  if (c->variant == MOPT_KERNEL_LITERAL) return false;
+  if (c->variant == MOPT_KERNEL_MOMENTS_ALWAYS || c->model != kModelPoint2Point) return true;
+  return !(jac_mode == MOPT_JAC_ANALYTIC_LEFT && leftBasisMayCancel(c));
 }
 }  // namespace
 
@@ -1702,7 +1751,25 @@ int mopt_point2point_set_data(mopt_cost *c, const void *src_xyz, const void *tgt
       MOPT_HIP_TRY(mopt::launchRelayoutP2P<float>(
           static_cast<const float *>(st.a), static_cast<const float *>(st.b), count,
           static_cast<float *>(c->d_tiles), c->num_tiles, c->stream));
+    // the scale of the scene (leftBasisCancels, hasSmallForwardStep); d_result is idle: the cost was quiesced
+    unsigned long long *d_box = reinterpret_cast<unsigned long long *>(c->d_result);
+    unsigned long long box[6];
+    MOPT_HIP_TRY(c->scalar_bytes == 8
+                     ? mopt::launchSourceBox<double>(static_cast<const double *>(c->d_tiles), count, d_box, c->stream)
+                     : mopt::launchSourceBox<float>(static_cast<const float *>(c->d_tiles), count, d_box, c->stream));
+    MOPT_HIP_TRY(hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
     MOPT_HIP_TRY(hipStreamSynchronize(c->stream));
+    double diag2 = 0.0, center2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      const double lo = mopt::sourceBoxValue(box[k]), hi = mopt::sourceBoxValue(box[3 + k]);
+      c->src_center[k] = 0.5 * (lo + hi);
+      diag2 += (hi - lo) * (hi - lo);
+      center2 += c->src_center[k] * c->src_center[k];
+    }
+    c->src_radius = 0.5 * std::sqrt(diag2);
+    c->src_bound = std::sqrt(center2) + c->src_radius;
+  } else {
+    c->src_center[0] = c->src_center[1] = c->src_center[2] = c->src_radius = c->src_bound = 0.0;
   }
   return MOPT_OK;
 }

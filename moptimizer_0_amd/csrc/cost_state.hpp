@@ -109,6 +109,11 @@ struct mopt_cost {
   long long data_stride = 0;  // scalar models: elements per data plane
   long long count = 0;
   int num_tiles = 0;
+  // point2point: the sources' bounding box as centre and half diagonal, and the bound of |p| they give
+  // (|centre| + radius), taken on the device when the data is laid out (mopt_point2point_set_data)
+  double src_center[3] = {0, 0, 0};
+  double src_radius = 0.0;
+  double src_bound = 0.0;
   int num_cus = 0;
   int max_grid = 0;
 

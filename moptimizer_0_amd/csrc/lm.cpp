@@ -153,7 +153,10 @@ int mopt_lm_minimize(mopt_cost *const *costs, int num_costs, const int *jacobian
                          merged ? last->d_partials + size_t(row_offset[k]) * row_length : nullptr);
     if (rc != MOPT_OK) return rc;
     costs[k]->cache.valid = false;
-    if (residentPerIterate(costs[k], jacobian_modes[k])) problem.fd_per_iterate = 1;
+    if (residentPerIterate(costs[k], jacobian_modes[k])) {
+      problem.fd_per_iterate = 1;
+      if (costs[k]->src_bound > problem.fd_source_bound) problem.fd_source_bound = costs[k]->src_bound;
+    }
     if (costs[k]->matcher) {
       problem.rematch = 1;               // its update(x) runs on the device, inside the loop
       costs[k]->state_version += 1;      // the correspondences will have changed

@@ -814,11 +814,14 @@ __device__ __forceinline__ bool lmStepBodyFor(const LmProblem &P, bool init, con
     if constexpr (!STATE_STAYS || CHOOSE_FD) {
       if (P.fd_per_iterate) {
         if (init) st.literal_points = 0;
-        if (propose)
+        if (propose) {
+          const double tx = double(next_x[0]), ty = double(next_x[1]), tz = double(next_x[2]);
+          const double threshold = forwardStepThreshold(P.fd_source_bound + sqrt(tx * tx + ty * ty + tz * tz));
           for (int i = 0; i < kNumParams; ++i) {
             const double a = fabs(double(next_x[i]));
-            if (a > 0.0 && a < 0.08) literal_next = 1;
+            if ((a > 0.0 ? a : 1.0) < threshold) literal_next = 1;  // (x_j = 0: the step of |x_j| = 1)
           }
+        }
         st.literal_points += literal_next;
       }
       if constexpr (CHOOSE_FD) *choice_out = literal_next;

@@ -211,12 +211,25 @@ struct LmControl {  // device memory; written by the step kernel only
 // [kLmGateMoments].done is ALL the sweep and the finalize kernel of a point2point cost read that
 // differentiates numerically under MOPT_KERNEL_AUTO / _MOMENTS (LmProblem::fd_per_iterate; one word, one
 // load): such kernels hold both forward-difference forms, and the step sets the word to kLmGateStopped
-// once the loop has stopped, else to kLmGateLiteralForm where the next point has some 0 < |x_j| < 0.08
+// once the loop has stopped, else to kLmGateLiteralForm where the next point has some 0 < |x_j| <
+// forwardStepThreshold(rho)
 // (the reference's own cancellation noise is part of its answer there, linearization.h:85-105), else to
 // kLmGateMomentsForm — so the sweep the blocking call would choose at that x is the one that runs.
 constexpr int kLmControlBlocks = 2;
 constexpr int kLmGateMoments = 1;
 constexpr int kLmGateMomentsForm = 0, kLmGateLiteralForm = 1, kLmGateStopped = 2;
+
+// Below which |x_j| forward differences are evaluated literally: 0.08 where the warped cloud lies
+// within rho = 30 of the origin (where it was measured), growing with rho = (bound of |p| stored when
+// the data was laid out) + |t| beyond — the reference's noise is eps rho / h_j (derivation at c_abi.cpp
+// hasSmallForwardStep).  One rule for the blocking calls and the step kernel.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+__host__ __device__
+#endif
+inline double forwardStepThreshold(double rho) {
+  const double scale = rho * (1.0 / 30.0);
+  return 0.08 * (scale > 1.0 ? scale : 1.0);
+}
 
 struct LmCostDesc {
   int model = 0;     // LmModel
@@ -257,6 +270,11 @@ struct LmProblem {
                               //    cost's finalize reduces them all: its result is the sum over the costs
   int fd_per_iterate = 0;     // 1: some point2point cost takes its forward differences by moments or
                               //    literally as each evaluated point asks (control[1], control[2])
+  double fd_source_bound = 0; // ... and the largest stored bound of |p| among those costs (forwardStepThreshold):
+                              //    one gate serves them all, so with several costs the loop may take the
+                              //    literal form at a point where the blocking call of the smaller cloud,
+                              //    which decides by its own bound, would still take the moments — more
+                              //    literal points, never fewer
   LmCostDesc cost[kLmMaxCosts];
   LmControl *control = nullptr;  // device
   void *state = nullptr;         // device, LmState<S> (lm_kernels.hip)
@@ -342,6 +360,25 @@ hipError_t launchRelayoutP2P(const S *src_xyz, const S *tgt_xyz, long long count
 hipError_t launchRelayoutReproj(const double *points_xyzw, const int32_t *pixels_uv,
                                 long long count, unsigned char *tiles, int num_tiles,
                                 hipStream_t stream);
+// Bounding box of the sources of laid-out tiles: box[0..2] the minima, box[3..5] the maxima, as
+// sourceBoxKey()s (six 64-bit words of device memory, initialised here).  decodeSourceBox() on the host.
+template <typename S>
+hipError_t launchSourceBox(const S *tiles, long long count, unsigned long long *d_box, hipStream_t stream);
+// a double as an unsigned key of the same order (negative values below positive ones)
+#if defined(__HIPCC__) || defined(__CUDACC__)
+__host__ __device__
+#endif
+inline unsigned long long sourceBoxKey(double v) {
+  unsigned long long bits;
+  __builtin_memcpy(&bits, &v, sizeof bits);
+  return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull);
+}
+inline double sourceBoxValue(unsigned long long key) {
+  const unsigned long long bits = (key >> 63) ? (key & 0x7fffffffffffffffull) : ~key;
+  double v;
+  __builtin_memcpy(&v, &bits, sizeof v);
+  return v;
+}
 
 // literal per-point evaluation; partials: [grid][kAccSym or kAccFull]
 template <typename S>

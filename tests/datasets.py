@@ -55,6 +55,71 @@ def synthetic_pair(n, seed=42, noise=0.0, dtype=np.float64):
     return src.astype(dtype), tgt.astype(dtype)
 
 
+# Scenes at the scales registration is run at (tests/test_gpu_scene_scale.py): where the source cloud
+# lies (offset added to a unit box scaled by `box`), where the pose under test sends it (`shift` of the
+# target's centroid against the source's), the target's noise and the translation error of the pose
+# under test, which with SCENE_ROTATION_ERROR keeps the residuals at a tenth of the cloud's size or so.
+SCENES = {
+    # the shape every other test uses: the control
+    "sensor": dict(box=(10, 10, 10), offset=(0, 0, 0), shift=(0, 0, 0), noise=0.01, dt=(0.3, -0.2, 0.25)),
+    # a site frame, a map frame: source and target in the same far frame
+    "site": dict(box=(10, 10, 10), offset=(1e3, 7e2, 10), shift=(0, 0, 0), noise=0.01, dt=(0.3, -0.2, 0.25)),
+    "map": dict(box=(10, 10, 10), offset=(1e5, 7e4, 1e3), shift=(0, 0, 0), noise=0.01, dt=(0.3, -0.2, 0.25)),
+    # a map-frame (UTM) scan registered to a target in a local frame: t ~ -R c
+    "utm_to_local": dict(box=(10, 10, 10), offset=(1e6, 7e5, 1e4), shift=(-1e6, -7e5, -1e4), noise=0.01,
+                         dt=(0.3, -0.2, 0.25)),
+    "utm_to_local_7e6": dict(box=(10, 10, 10), offset=(7e6, 4.9e6, 7e4), shift=(-7e6, -4.9e6, -7e4),
+                             noise=0.01, dt=(0.3, -0.2, 0.25)),
+    # ... and the other way round: a far translation
+    "local_to_map": dict(box=(10, 10, 10), offset=(0, 0, 0), shift=(1e6, 7e5, 1e4), noise=0.01,
+                         dt=(0.3, -0.2, 0.25)),
+    # a millimetre-sized object, a flat wall
+    "mm": dict(box=(1e-2, 1e-2, 1e-2), offset=(0, 0, 0), shift=(0, 0, 0), noise=1e-5, dt=(3e-4, -2e-4, 2.5e-4)),
+    "wall": dict(box=(100, 1, 0.01), offset=(0, 0, 0), shift=(0, 0, 0), noise=0.01, dt=(0.3, -0.2, 0.25)),
+}
+SCENE_ROTATION_ERROR = np.array([0.01, -0.02, 0.015])
+SCENE_SIZES = (4097, 513)  # eight fp64 tiles + 1; one + 1
+_SCENE_SEEDS = {name: 1000 + 17 * k for k, name in enumerate(SCENES)}
+
+
+def _exp_so3(w):
+    th = np.linalg.norm(w)
+    if th == 0:
+        return np.eye(3)
+    a = np.asarray(w) / th
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+
+
+def scene_pair(name, n, dtype=np.float64, rot=None, about_origin=False):
+    """(src, tgt, x) of a scene of SCENES: src ~ U[0, box] + offset; tgt = the source turned by the
+    fixture rotation about its centroid, moved by `shift`, + N(0, noise^2); x the pose under test —
+    rotation vector `rot` (default: the fixture's + SCENE_ROTATION_ERROR), translation such that the
+    source's centroid lands `dt` from the target's.  about_origin: the same-frame pose with a small
+    translation instead — tgt = Exp(rot) src + noise, a turn about the frame's origin, and
+    x = (dt, rot), so that |t| stays a fraction of a metre however far the cloud lies.  Fixed seed per
+    scene, everything rounded to `dtype` at the end."""
+    sc = SCENES[name]
+    rng = np.random.default_rng(_SCENE_SEEDS[name] + n)
+    src = rng.random((n, 3)) * np.array(sc["box"], dtype=np.float64) + np.array(sc["offset"], dtype=np.float64)
+    if about_origin:
+        w = np.zeros(3) if rot is None else np.asarray(rot, dtype=np.float64)
+        R = _exp_so3(w).astype(np.longdouble)
+        tgt = np.asarray(src.astype(np.longdouble) @ R.T, dtype=np.float64)
+        tgt = tgt + rng.normal(0.0, sc["noise"], size=src.shape)
+        x = np.concatenate([np.array(sc["dt"], dtype=np.float64), w])
+        return src.astype(dtype), tgt.astype(dtype), x.astype(dtype)
+    c = src.mean(axis=0)
+    c_tgt = c + np.array(sc["shift"], dtype=np.float64)
+    tgt = (src - c) @ fixture_rotation().T + c_tgt + rng.normal(0.0, sc["noise"], size=src.shape)
+    w = FIXTURE_X[3:] + SCENE_ROTATION_ERROR if rot is None else np.asarray(rot, dtype=np.float64)
+    # t = c_tgt - R_x c + dt, the product in long double: at a 1e7 offset its fp64 rounding is 1e-9
+    Rc = (_exp_so3(w).astype(np.longdouble) @ c.astype(np.longdouble))
+    t = np.asarray(c_tgt.astype(np.longdouble) - Rc, dtype=np.float64) + np.array(sc["dt"])
+    x = np.concatenate([t, w])
+    return src.astype(dtype), tgt.astype(dtype), x.astype(dtype)
+
+
 def synthetic_camera(n, seed=7, x_true=(-0.01, 0.02, -0.058, 0.018, -0.0013, 0.027)):
     """Points in front of the camera of tst/camera_calibration.cpp and the rounded pixels their
     projection under x_true lands on."""

@@ -168,6 +168,100 @@ def test_ragged_sizes(hip_lib, oracle, n):
     assert abs(c - want) <= REL * abs(want)
 
 
+# sweep.hpp kReprojTilePoints (= kBlockThreads: one element per lane of a workgroup).  The library
+# exports no accessor for it: if that constant changes, change this one, or the sizes below stop being
+# tile boundaries.
+REPROJ_TILE = 256
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, REPROJ_TILE - 1, REPROJ_TILE, REPROJ_TILE + 1,
+                               2 * REPROJ_TILE + 1])
+def test_ragged_sizes_reprojection(hip_lib, oracle, n):
+    """The reprojection sweep runs on the tiled skeleton of point2point with a tile of its own, whose
+    tail repeats the last element (relayoutReprojKernel): counts around a wavefront and a tile."""
+    pts, pix = ds.synthetic_camera(max(n, 1), seed=n + 3)
+    pts, pix = pts[:n], pix[:n]
+    if n == 0:
+        with pytest.raises(hip_lib.MoptError, match="Empty point / pixel list"):
+            hip_lib.ReprojectionCost(pts, pix)
+        return
+    cost = hip_lib.ReprojectionCost(pts, pix)
+    x = np.array([0.05, -0.02, 0.03, 0.02, -0.01, 0.03])
+    for cov in (None, np.array([[2.0, 0.5], [0.1, 0.7]])):
+        for loss_kind, loss_param in ((0, 0.0), (1, 100.0)):
+            cost.set_covariance(cov)
+            cost.set_loss(loss_kind, loss_param)
+            want = oracle.camera_linearize(pts, pix, x, cov=cov, loss_kind=loss_kind, loss_param=loss_param)
+            check(cost.linearize(x, 2), want, tol=REL)
+            want_cost = oracle.camera_cost(pts, pix, x)
+            assert abs(cost.compute_cost(x) - want_cost) <= REL * want_cost
+    cost.close()
+
+
+def exp_curve_float_linearize(t, y, x, loss):
+    """linearization.h:65-124 over y - exp(m t + c) in float arithmetic: the reference's exp-curve
+    model is written in double only and so is the oracle's, while the device model is instantiated
+    in float too.  Each operation rounded to float, the three sums in double."""
+    f = np.float32
+    t, y, x = t.astype(f), y.astype(f), x.astype(f)
+    r = y - np.exp(x[0] * t + x[1], dtype=f)
+    J = np.empty((t.shape[0], 2), dtype=f)
+    for j in range(2):
+        h = np.sqrt(np.finfo(f).eps) * np.abs(x[j])
+        xp = x.copy()
+        xp[j] = x[j] + h
+        J[:, j] = ((y - np.exp(xp[0] * t + xp[1], dtype=f)) - r) / h
+    rr = r * r
+    w = np.ones_like(rr) if loss is None else (f(loss) * f(loss)) / ((rr + f(loss)) * (rr + f(loss)))
+    wJ = (w[:, None] * J).astype(np.float64)
+    return wJ.T @ J.astype(np.float64), wJ.T @ r.astype(np.float64), rr.astype(np.float64).sum()
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("kind", ["exp_curve", "rational"])
+def test_ragged_sizes_scalar_models(hip_lib, oracle, kind, dtype):
+    """The built-in scalar models: a workgroup takes 256 packs of 16 bytes (512 fp64 / 1024 fp32
+    elements, c_abi.cpp scalarGrid); counts around a pack, a wavefront and that tile.  Tolerances of
+    test_small_parametric_models_match_oracle."""
+    tile = 256 * (16 // np.dtype(dtype).itemsize)
+    rng = np.random.default_rng(14)
+    top = 2 * tile + 1
+    if kind == "exp_curve":
+        model, oracle_kind, modes = hip_lib.capi.MODEL_EXP_CURVE, 1, (True,)
+        t = np.linspace(0.0, 4.95, top)
+        y = np.exp(0.3 * t + 0.1) + rng.normal(0, 0.2, t.shape)
+        # (fp32: steps sqrt(eps_f) |x_j| of 4e-4 and more, so that one ulp of expf between the device's
+        # and the host's math library, eps_f / h_j per Jacobian entry, stays 10 x below the fp32 tolerance)
+        x = np.array([0.29, 0.13] if dtype == np.float64 else [1.2, 2.0], dtype=dtype)
+    else:
+        model, oracle_kind, modes = hip_lib.capi.MODEL_RATIONAL, 2, (True, False)
+        t = np.abs(rng.normal(1.0, 1.0, top)) + 0.05
+        y = 0.36 * t / (0.56 + t) + rng.normal(0, 0.01, t.shape)
+        x = np.array([0.9, 0.2], dtype=dtype)
+    with pytest.raises(hip_lib.MoptError, match="bad data arrays / count"):
+        hip_lib.ScalarModelCost(model, t[:0], y[:0], dtype=dtype)
+    for n in (1, 2, 63, 64, 65, tile - 1, tile, tile + 1, top):
+        c = hip_lib.ScalarModelCost(model, t[:n], y[:n], dtype=dtype)
+        for numeric in modes:
+            for lk, lp in ((0, 0.0), (1, 100.0)):
+                c.set_loss(lk, lp)
+                if kind == "exp_curve" and dtype == np.float32:
+                    want = exp_curve_float_linearize(t[:n], y[:n], x, lp if lk else None)
+                else:
+                    want = oracle.scalar_linearize(oracle_kind, t[:n], y[:n], x, numeric=numeric, loss_kind=lk,
+                                                   loss_param=lp, dtype=dtype)
+                want = tuple(np.asarray(v, dtype=np.float64) for v in want)
+                if dtype == np.float32:
+                    tol = 5e-3
+                else:
+                    tol = fd_tolerance_libm(x) if numeric else REL
+                try:
+                    check(c.linearize(x, 2 if numeric else 0), want, tol=tol)
+                except AssertionError as e:
+                    raise AssertionError((n, numeric, lk) + e.args)
+        c.close()
+
+
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 1023, 1025, 4097, 30_011])
 def test_ragged_sizes_float32_forward_differences(hip_lib, oracle, n):
     """The fp32 forward-difference sweep takes the four points of a pack as two pairs in packed
