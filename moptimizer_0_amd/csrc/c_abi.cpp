@@ -361,7 +361,7 @@ int p2pLinearizeAsync(mopt_cost *c, int jac_mode, const S *x, double *d_result, 
     // analytic patterns stream like the moments sweep: one (70.8 vs 72.1 us at 10 M, and half the
     // partial rows for the finalize kernel)
     const int grid = gridFor(c, blocksPerCu(jac_mode == MOPT_JAC_NUMERIC ? 2 : 1));
-    const int nacc = c->cov_mode == mopt::kCovGeneral ? mopt::kAccFull : mopt::kAccSym;
+    const int nacc = mopt::denseRowLength(c->cov_mode);
     // (tiled launch signature: dispatch timestamps like the moments sweep)
     SweepTimer timer(c, s, true);
     MOPT_HIP_TRY(mopt::launchP2PLinearizeLiteral<S>(args, jac_mode, c->cov_mode, grid, timer.site));
@@ -443,7 +443,7 @@ int reprojLinearizeAsync(mopt_cost *c, int jac_mode, const double *x, double *d_
   mopt::ReprojSweepArgs args;
   fillReprojArgs(c, x, true, args);
   const int grid = gridFor(c, blocksPerCu(2));
-  const int nacc = c->cov_mode == mopt::kCovGeneral ? mopt::kAccFull : mopt::kAccSym;
+  const int nacc = mopt::denseRowLength(c->cov_mode);
   SweepTimer timer(c, s, true);
   MOPT_HIP_TRY(mopt::launchReprojLinearize(args, c->cov_mode, grid, timer.site));
   timer.stop();
@@ -486,6 +486,20 @@ bool scalarModelHasJacobian(int kind) {
   return kind != mopt::kScalarExpCurve && kind != mopt::kScalarExpCurveMarked;
 }
 
+// The Jacobian modes of the generic models (built-in scalar and run-time compiled; blocking calls and
+// the device-resident loop): forward differences always, the model's own where it has one.
+int checkModelJacobian(const mopt_cost *c, int jac_mode) {
+  if (jac_mode == MOPT_JAC_ANALYTIC_TST_LAYOUT || jac_mode == MOPT_JAC_ANALYTIC_LEFT ||
+      jac_mode == MOPT_JAC_ANALYTIC_RIGHT)
+    return fail(MOPT_ERR_UNSUPPORTED,
+                "the as-written layout and the perturbation Jacobians apply to point2point only");
+  const bool has_jacobian =
+      c->model == kModelJit ? c->jit.has_jacobian : scalarModelHasJacobian(c->scalar_model);
+  if (jac_mode == MOPT_JAC_ANALYTIC && !has_jacobian)
+    return fail(MOPT_ERR_UNSUPPORTED, "Non implemented non-jacobian model function `f_df` being used.");
+  return MOPT_OK;
+}
+
 // workgroups (= partial rows) of a built-in scalar model's sweep: a workgroup per 256 packs of 16
 // bytes, at most four per CU
 int scalarGrid(const mopt_cost *c) {
@@ -499,13 +513,8 @@ template <typename S>
 int scalarSweepAsync(mopt_cost *c, bool cost_only, int jac_mode, const S *x, double *d_out,
                      hipStream_t s, const mopt::HostPublish &pub) {
   if (!cost_only) {
-    if (jac_mode == MOPT_JAC_ANALYTIC_TST_LAYOUT || jac_mode == MOPT_JAC_ANALYTIC_LEFT ||
-        jac_mode == MOPT_JAC_ANALYTIC_RIGHT)
-      return fail(MOPT_ERR_UNSUPPORTED,
-                  "the as-written layout and the perturbation Jacobians apply to point2point only");
-    if (jac_mode == MOPT_JAC_ANALYTIC && !scalarModelHasJacobian(c->scalar_model))
-      return fail(MOPT_ERR_UNSUPPORTED,
-                  "Non implemented non-jacobian model function `f_df` being used.");
+    const int rc = checkModelJacobian(c, jac_mode);
+    if (rc != MOPT_OK) return rc;
   }
   mopt::ScalarSweepArgs<S> args;
   fillScalarArgs<S>(c, x, args);
@@ -518,9 +527,8 @@ int scalarSweepAsync(mopt_cost *c, bool cost_only, int jac_mode, const S *x, dou
   if (cost_only) {
     MOPT_HIP_TRY(mopt::launchFinalizeCost(c->d_partials, grid, d_out, pub, s, c->launch_peers, timer.aql()));
   } else {
-    const int nacc = c->cov_mode == mopt::kCovGeneral ? n * n + n + 1 : n * (n + 1) / 2 + n + 1;
-    MOPT_HIP_TRY(mopt::launchFinalizeDense(c->d_partials, grid, nacc, n, d_out, pub, s, c->launch_peers,
-                                           timer.aql()));
+    MOPT_HIP_TRY(mopt::launchFinalizeDense(c->d_partials, grid, mopt::denseRowLength(n, c->cov_mode), n,
+                                           d_out, pub, s, c->launch_peers, timer.aql()));
   }
   return MOPT_OK;
 }
@@ -575,21 +583,20 @@ int jitGrid(const mopt_cost *c) {
   return int(blocks);
 }
 
+// rows of a run-time compiled model's sweep (the column-per-lane sweep of a wide one has one form)
+int jitDenseRow(const mopt_cost *c) {
+  return mopt::denseRowLength(c->n_params, c->jit.wide ? int(mopt::kCovGeneral) : c->cov_mode);
+}
+
 // User-defined (hipRTC) model: same sweep shape as the built-in scalar models, full-form rows.
 template <typename S>
 int jitSweepAsync(mopt_cost *c, bool cost_only, int jac_mode, const S *x, double *d_out,
                   hipStream_t s, const mopt::HostPublish &pub) {
   if (!cost_only) {
-    if (jac_mode == MOPT_JAC_ANALYTIC_TST_LAYOUT || jac_mode == MOPT_JAC_ANALYTIC_LEFT ||
-        jac_mode == MOPT_JAC_ANALYTIC_RIGHT)
-      return fail(MOPT_ERR_UNSUPPORTED,
-                  "the as-written layout and the perturbation Jacobians apply to point2point only");
-    if (jac_mode == MOPT_JAC_ANALYTIC && !c->jit.has_jacobian)
-      return fail(MOPT_ERR_UNSUPPORTED,
-                  "Non implemented non-jacobian model function `f_df` being used.");
+    const int rc = checkModelJacobian(c, jac_mode);
+    if (rc != MOPT_OK) return rc;
   }
   const int mode = cost_only ? 0 : (jac_mode == MOPT_JAC_NUMERIC ? 2 : 1);
-  const bool cov_symmetric = !c->jit.wide && c->cov_mode != mopt::kCovGeneral;
   const mopt::JitVariant *variant = mopt::jitVariant(c->jit, mode, c->cov_mode);
   if (!variant) return fail(MOPT_ERR_INVALID_ARGUMENT, mopt::jitLastError());
   const int grid = jitGrid(c);
@@ -608,8 +615,8 @@ int jitSweepAsync(mopt_cost *c, bool cost_only, int jac_mode, const S *x, double
   if (cost_only) {
     MOPT_HIP_TRY(mopt::launchFinalizeCost(c->d_partials, grid, d_out, pub, s, c->launch_peers));
   } else {
-    const int nacc = cov_symmetric ? n * (n + 1) / 2 + n + 1 : n * n + n + 1;
-    MOPT_HIP_TRY(mopt::launchFinalizeDense(c->d_partials, grid, nacc, n, d_out, pub, s, c->launch_peers));
+    MOPT_HIP_TRY(mopt::launchFinalizeDense(c->d_partials, grid, jitDenseRow(c), n, d_out, pub, s,
+                                           c->launch_peers));
   }
   return MOPT_OK;
 }
@@ -621,40 +628,28 @@ int linearizeAsyncImpl(mopt_cost *c, int jac_mode, const void *x, double *d_resu
                        const mopt::HostPublish &pub) {
   if (jac_mode < MOPT_JAC_ANALYTIC || jac_mode > MOPT_JAC_ANALYTIC_RIGHT)
     return fail(MOPT_ERR_INVALID_ARGUMENT, "unknown jacobian_mode");
-  if (c->model == kModelJit)
-    return c->scalar_bytes == 8
-               ? jitSweepAsync<double>(c, false, jac_mode, static_cast<const double *>(x), d_result,
-                                       s, pub)
-               : jitSweepAsync<float>(c, false, jac_mode, static_cast<const float *>(x), d_result, s,
-                                      pub);
-  if (c->model == kModelScalar)
-    return c->scalar_bytes == 8
-               ? scalarSweepAsync<double>(c, false, jac_mode, static_cast<const double *>(x),
-                                          d_result, s, pub)
-               : scalarSweepAsync<float>(c, false, jac_mode, static_cast<const float *>(x),
-                                         d_result, s, pub);
   if (c->model == kModelReprojection)
     return reprojLinearizeAsync(c, jac_mode, static_cast<const double *>(x), d_result, s, pub);
-  if (c->scalar_bytes == 8)
-    return p2pLinearizeAsync<double>(c, jac_mode, static_cast<const double *>(x), d_result, s, pub);
-  return p2pLinearizeAsync<float>(c, jac_mode, static_cast<const float *>(x), d_result, s, pub);
+  return withScalar(c->scalar_bytes, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    const S *xs = static_cast<const S *>(x);
+    if (c->model == kModelJit) return jitSweepAsync<S>(c, false, jac_mode, xs, d_result, s, pub);
+    if (c->model == kModelScalar) return scalarSweepAsync<S>(c, false, jac_mode, xs, d_result, s, pub);
+    return p2pLinearizeAsync<S>(c, jac_mode, xs, d_result, s, pub);
+  });
 }
 
 int costAsyncImpl(mopt_cost *c, const void *x, double *d_sum, hipStream_t s,
                   const mopt::HostPublish &pub) {
-  if (c->model == kModelJit)
-    return c->scalar_bytes == 8
-               ? jitSweepAsync<double>(c, true, 0, static_cast<const double *>(x), d_sum, s, pub)
-               : jitSweepAsync<float>(c, true, 0, static_cast<const float *>(x), d_sum, s, pub);
-  if (c->model == kModelScalar)
-    return c->scalar_bytes == 8
-               ? scalarSweepAsync<double>(c, true, 0, static_cast<const double *>(x), d_sum, s, pub)
-               : scalarSweepAsync<float>(c, true, 0, static_cast<const float *>(x), d_sum, s, pub);
   if (c->model == kModelReprojection)
     return reprojCostAsync(c, static_cast<const double *>(x), d_sum, s, pub);
-  if (c->scalar_bytes == 8)
-    return p2pCostAsync<double>(c, static_cast<const double *>(x), d_sum, s, pub);
-  return p2pCostAsync<float>(c, static_cast<const float *>(x), d_sum, s, pub);
+  return withScalar(c->scalar_bytes, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    const S *xs = static_cast<const S *>(x);
+    if (c->model == kModelJit) return jitSweepAsync<S>(c, true, 0, xs, d_sum, s, pub);
+    if (c->model == kModelScalar) return scalarSweepAsync<S>(c, true, 0, xs, d_sum, s, pub);
+    return p2pCostAsync<S>(c, xs, d_sum, s, pub);
+  });
 }
 
 }  // namespace mopt_detail
@@ -951,6 +946,22 @@ int uploadArgs(mopt_cost *c, const Args &host_value, hipStream_t s) {
   return MOPT_OK;
 }
 
+// A generic model's argument block (x[] | h[] inside it, of Args' own length): where the step kernel
+// writes them, and, when `stale`, the static part (data, loss, covariance; filled at x = 0) uploaded.
+template <typename Args, typename S>
+int residentPrepareModel(mopt_cost *c, void (*fill)(const mopt_cost *, const S *, Args &), bool stale,
+                         double *partials, hipStream_t s, mopt::LmCostDesc *desc) {
+  constexpr int kSlots = int(sizeof(Args::x) / sizeof(S));
+  desc->x_slots = kSlots;
+  desc->x_offset = int(offsetof(Args, x));
+  if (!stale) return MOPT_OK;
+  Args args;
+  const S zero[kSlots] = {0};
+  fill(c, zero, args);
+  args.partials = partials;
+  return uploadArgs(c, args, s);
+}
+
 template <typename S>
 int residentPrepareP2P(mopt_cost *c, int jac_mode, bool moments, double *partials, hipStream_t s) {
   mopt::P2PSweepArgs<S> args;
@@ -1014,18 +1025,16 @@ int residentGrid(const mopt_cost *c, int jac_mode) {
 }
 
 int residentDenseRow(const mopt_cost *c, int jac_mode) {
-  const int n = c->n_params;
   switch (c->model) {
     case kModelPoint2Point:
       if (usesMoments(c, jac_mode)) return 0;  // rows of moments, contracted by their own finalize kernel
-      return c->cov_mode == mopt::kCovGeneral ? mopt::kAccFull : mopt::kAccSym;
+      return mopt::denseRowLength(c->cov_mode);
     case kModelReprojection:
-      return c->cov_mode == mopt::kCovGeneral ? mopt::kAccFull : mopt::kAccSym;
+      return mopt::denseRowLength(c->cov_mode);
     case kModelJit:
-      if (c->jit.wide) return n * n + n + 1;  // the column-per-lane sweep has one row form
-      return c->cov_mode == mopt::kCovGeneral ? n * n + n + 1 : n * (n + 1) / 2 + n + 1;
+      return jitDenseRow(c);
     case kModelScalar:
-      return c->cov_mode == mopt::kCovGeneral ? n * n + n + 1 : n * (n + 1) / 2 + n + 1;
+      return mopt::denseRowLength(c->n_params, c->cov_mode);
     default:
       return 0;
   }
@@ -1049,9 +1058,9 @@ int residentPrepare(mopt_cost *c, int jac_mode, hipStream_t s, mopt::LmCostDesc 
       desc->model = mopt::kLmPoint2Point;
       desc->moments = usesMoments(c, jac_mode) ? 1 : 0;
       if (stale)
-        rc = c->scalar_bytes == 8
-                 ? residentPrepareP2P<double>(c, jac_mode, desc->moments, partials, s)
-                 : residentPrepareP2P<float>(c, jac_mode, desc->moments, partials, s);
+        rc = withScalar(c->scalar_bytes, [&](auto scalar) {
+          return residentPrepareP2P<typename decltype(scalar)::type>(c, jac_mode, desc->moments, partials, s);
+        });
       break;
     }
     case kModelReprojection: {
@@ -1071,83 +1080,28 @@ int residentPrepare(mopt_cost *c, int jac_mode, hipStream_t s, mopt::LmCostDesc 
       break;
     }
     case kModelScalar: {
-      if (jac_mode == MOPT_JAC_ANALYTIC_TST_LAYOUT || jac_mode == MOPT_JAC_ANALYTIC_LEFT ||
-        jac_mode == MOPT_JAC_ANALYTIC_RIGHT)
-        return fail(MOPT_ERR_UNSUPPORTED,
-                    "the as-written layout and the perturbation Jacobians apply to point2point only");
-      if (jac_mode == MOPT_JAC_ANALYTIC && !scalarModelHasJacobian(c->scalar_model))
-        return fail(MOPT_ERR_UNSUPPORTED,
-                    "Non implemented non-jacobian model function `f_df` being used.");
+      rc = checkModelJacobian(c, jac_mode);
+      if (rc != MOPT_OK) return rc;
       desc->model = mopt::kLmScalar;
-      desc->x_offset = c->scalar_bytes == 8 ? int(offsetof(mopt::ScalarSweepArgs<double>, x))
-                                            : int(offsetof(mopt::ScalarSweepArgs<float>, x));
-      if (stale) {
-        if (c->scalar_bytes == 8) {
-          mopt::ScalarSweepArgs<double> args;
-          const double zero[mopt::kMaxParams] = {0};
-          fillScalarArgs<double>(c, zero, args);
-          args.partials = partials;
-          rc = uploadArgs(c, args, s);
-        } else {
-          mopt::ScalarSweepArgs<float> args;
-          const float zero[mopt::kMaxParams] = {0};
-          fillScalarArgs<float>(c, zero, args);
-          args.partials = partials;
-          rc = uploadArgs(c, args, s);
-        }
-      }
+      rc = withScalar(c->scalar_bytes, [&](auto scalar) {
+        using S = typename decltype(scalar)::type;
+        return residentPrepareModel<mopt::ScalarSweepArgs<S>>(c, fillScalarArgs<S>, stale, partials, s, desc);
+      });
       break;
     }
     case kModelJit: {
-      if (jac_mode == MOPT_JAC_ANALYTIC_TST_LAYOUT || jac_mode == MOPT_JAC_ANALYTIC_LEFT ||
-        jac_mode == MOPT_JAC_ANALYTIC_RIGHT)
-        return fail(MOPT_ERR_UNSUPPORTED,
-                    "the as-written layout and the perturbation Jacobians apply to point2point only");
-      if (jac_mode == MOPT_JAC_ANALYTIC && !c->jit.has_jacobian)
-        return fail(MOPT_ERR_UNSUPPORTED,
-                    "Non implemented non-jacobian model function `f_df` being used.");
+      rc = checkModelJacobian(c, jac_mode);
+      if (rc != MOPT_OK) return rc;
       // compile (first use) before anything is queued: a source error must surface here
       if (!mopt::jitVariant(c->jit, jac_mode == MOPT_JAC_NUMERIC ? 2 : 1, c->cov_mode))
         return fail(MOPT_ERR_INVALID_ARGUMENT, mopt::jitLastError());
       desc->model = mopt::kLmJit;
-      if (c->jit.wide) {  // x[16] | h[16] in the wide sweep's argument block
-        desc->x_slots = mopt::kMaxWideParams;
-        desc->x_offset = c->scalar_bytes == 8 ? int(offsetof(mopt::JitWideArgs<double>, x))
-                                              : int(offsetof(mopt::JitWideArgs<float>, x));
-        if (stale) {
-          if (c->scalar_bytes == 8) {
-            mopt::JitWideArgs<double> args;
-            const double zero[mopt::kMaxWideParams] = {0};
-            fillJitWideArgs<double>(c, zero, args);
-            args.partials = partials;
-            rc = uploadArgs(c, args, s);
-          } else {
-            mopt::JitWideArgs<float> args;
-            const float zero[mopt::kMaxWideParams] = {0};
-            fillJitWideArgs<float>(c, zero, args);
-            args.partials = partials;
-            rc = uploadArgs(c, args, s);
-          }
-        }
-        break;
-      }
-      desc->x_offset = c->scalar_bytes == 8 ? int(offsetof(mopt::JitArgs<double>, x))
-                                            : int(offsetof(mopt::JitArgs<float>, x));
-      if (stale) {
-        if (c->scalar_bytes == 8) {
-          mopt::JitArgs<double> args;
-          const double zero[mopt::kMaxParams] = {0};
-          fillJitArgs<double>(c, zero, args);
-          args.partials = partials;
-          rc = uploadArgs(c, args, s);
-        } else {
-          mopt::JitArgs<float> args;
-          const float zero[mopt::kMaxParams] = {0};
-          fillJitArgs<float>(c, zero, args);
-          args.partials = partials;
-          rc = uploadArgs(c, args, s);
-        }
-      }
+      rc = withScalar(c->scalar_bytes, [&](auto scalar) {
+        using S = typename decltype(scalar)::type;
+        if (c->jit.wide)  // x[16] | h[16] in the wide sweep's argument block
+          return residentPrepareModel<mopt::JitWideArgs<S>>(c, fillJitWideArgs<S>, stale, partials, s, desc);
+        return residentPrepareModel<mopt::JitArgs<S>>(c, fillJitArgs<S>, stale, partials, s, desc);
+      });
       break;
     }
     default:
@@ -1229,20 +1183,16 @@ int residentSweepSet(mopt_cost *const *costs, int num_costs, const int *jac_mode
       MOPT_HIP_TRY(mopt::launchReprojResidentSet(set, control, first->cov_mode, site));
       return MOPT_OK;
     case kModelPoint2Point:
-      if (first->scalar_bytes == 8)
-        MOPT_HIP_TRY(mopt::launchP2PLiteralResidentSet<double>(set, control, jac_mode,
-                                                               first->cov_mode, site));
-      else
-        MOPT_HIP_TRY(mopt::launchP2PLiteralResidentSet<float>(set, control, jac_mode,
-                                                              first->cov_mode, site));
+      MOPT_HIP_TRY(withScalar(first->scalar_bytes, [&](auto scalar) {
+        return mopt::launchP2PLiteralResidentSet<typename decltype(scalar)::type>(set, control, jac_mode,
+                                                                                  first->cov_mode, site);
+      }));
       return MOPT_OK;
     case kModelScalar:
-      if (first->scalar_bytes == 8)
-        MOPT_HIP_TRY(mopt::launchScalarModelResidentSet<double>(set, control, first->scalar_model,
-                                                                jac_mode, first->cov_mode, s));
-      else
-        MOPT_HIP_TRY(mopt::launchScalarModelResidentSet<float>(set, control, first->scalar_model,
-                                                               jac_mode, first->cov_mode, s));
+      MOPT_HIP_TRY(withScalar(first->scalar_bytes, [&](auto scalar) {
+        return mopt::launchScalarModelResidentSet<typename decltype(scalar)::type>(
+            set, control, first->scalar_model, jac_mode, first->cov_mode, s);
+      }));
       return MOPT_OK;
     case kModelJit: {
       const mopt::JitVariant *variant =
@@ -1256,9 +1206,11 @@ int residentSweepSet(mopt_cost *const *costs, int num_costs, const int *jac_mode
   }
 }
 
-int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStream_t s,
-                  unsigned long long base_sequence, const mopt::LmProblem *step, int own_index,
-                  bool finalize) {
+namespace {
+template <typename S>
+int residentSweepFor(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStream_t s,
+                     unsigned long long base_sequence, const mopt::LmProblem *step, int own_index,
+                     bool finalize) {
   mopt::PeerCombine pc;
   const mopt::PeerCombine *peers = nullptr;
   if (c->combine.mode == MOPT_COMBINE_PEER) {
@@ -1279,20 +1231,15 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
   if (c->matcher) {
     // the model's update(x): re-search the correspondences at the point the step kernel has just
     // proposed, when it says so (a linearization point), before that point is swept
-    if (c->scalar_bytes == 8) {
-      mopt::IcpMatchArgs<double> a;
-      fillIcpArgs<double>(c, a);
-      MOPT_HIP_TRY(mopt::launchIcpMatchResident<double>(
-          a, static_cast<const mopt::P2PSweepArgs<double> *>(c->d_lm_args), control, s));
-    } else {
-      mopt::IcpMatchArgs<float> a;
-      fillIcpArgs<float>(c, a);
-      MOPT_HIP_TRY(mopt::launchIcpMatchResident<float>(
-          a, static_cast<const mopt::P2PSweepArgs<float> *>(c->d_lm_args), control, s));
-    }
+    mopt::IcpMatchArgs<S> a;
+    fillIcpArgs<S>(c, a);
+    MOPT_HIP_TRY(mopt::launchIcpMatchResident<S>(
+        a, static_cast<const mopt::P2PSweepArgs<S> *>(c->d_lm_args), control, s));
   }
   switch (c->model) {
     case kModelPoint2Point: {
+      const S *tiles = static_cast<const S *>(c->d_tiles);
+      const mopt::P2PSweepArgs<S> *d_args = static_cast<const mopt::P2PSweepArgs<S> *>(c->d_lm_args);
       if (residentPerIterate(c, jac_mode)) {
         // one sweep launch that holds both forward-difference forms and runs the one the step kernel named
         // for this point (sweep.hpp kLmGateMoments), and one finalize kernel that reads which it was
@@ -1302,17 +1249,9 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
         // 2 — measured 82.8-83.5 against 84.8-85.7 us per sweep at 10 M, 18.7 against 21.2 at 1 M
         static const int moments_blocks = envInt("MOPT_LM_EITHER_MOMENTS_BLOCKS", 1);
         const int grid_m = moments_blocks >= 2 ? grid_l : std::min(grid_l, residentGrid(c, jac_mode));
-        const int nacc = c->cov_mode == mopt::kCovGeneral ? mopt::kAccFull : mopt::kAccSym;
-        if (c->scalar_bytes == 8)
-          MOPT_HIP_TRY(mopt::launchForwardDiffEitherResident<double>(
-              static_cast<const double *>(c->d_tiles), c->num_tiles,
-              static_cast<const mopt::P2PSweepArgs<double> *>(c->d_lm_args), control, c->cov_mode, grid_l,
-              grid_m, site));
-        else
-          MOPT_HIP_TRY(mopt::launchForwardDiffEitherResident<float>(
-              static_cast<const float *>(c->d_tiles), c->num_tiles,
-              static_cast<const mopt::P2PSweepArgs<float> *>(c->d_lm_args), control, c->cov_mode, grid_l,
-              grid_m, site));
+        const int nacc = mopt::denseRowLength(c->cov_mode);
+        MOPT_HIP_TRY(mopt::launchForwardDiffEitherResident<S>(tiles, c->num_tiles, d_args, control,
+                                                              c->cov_mode, grid_l, grid_m, site));
         if (finalize)
           MOPT_HIP_TRY(mopt::launchFinalizeEitherResident(c->d_partials, grid_m, grid_l, nacc, c->d_lm_basis,
                                                           c->d_result, control, s, peers, step, own_index,
@@ -1321,14 +1260,7 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
       }
       if (usesMoments(c, jac_mode)) {
         const int grid = residentGrid(c, jac_mode);
-        if (c->scalar_bytes == 8)
-          MOPT_HIP_TRY(mopt::launchP2PMomentsResident<double>(
-              static_cast<const double *>(c->d_tiles), c->num_tiles,
-              static_cast<const mopt::P2PSweepArgs<double> *>(c->d_lm_args), control, grid, site));
-        else
-          MOPT_HIP_TRY(mopt::launchP2PMomentsResident<float>(
-              static_cast<const float *>(c->d_tiles), c->num_tiles,
-              static_cast<const mopt::P2PSweepArgs<float> *>(c->d_lm_args), control, grid, site));
+        MOPT_HIP_TRY(mopt::launchP2PMomentsResident<S>(tiles, c->num_tiles, d_args, control, grid, site));
         if (finalize)
           MOPT_HIP_TRY(mopt::launchFinalizeMomentsResident(c->d_partials, grid, c->d_lm_basis,
                                                          c->d_result, control, s, peers, step,
@@ -1336,14 +1268,7 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
       } else {
         const int grid = residentGrid(c, jac_mode);
         const int nacc = residentDenseRow(c, jac_mode);
-        if (c->scalar_bytes == 8)
-          MOPT_HIP_TRY(mopt::launchP2PLiteralResident<double>(
-              static_cast<const mopt::P2PSweepArgs<double> *>(c->d_lm_args), control, jac_mode,
-              c->cov_mode, grid, site));
-        else
-          MOPT_HIP_TRY(mopt::launchP2PLiteralResident<float>(
-              static_cast<const mopt::P2PSweepArgs<float> *>(c->d_lm_args), control, jac_mode,
-              c->cov_mode, grid, site));
+        MOPT_HIP_TRY(mopt::launchP2PLiteralResident<S>(d_args, control, jac_mode, c->cov_mode, grid, site));
         if (finalize)
           MOPT_HIP_TRY(mopt::launchFinalizeDenseResident(c->d_partials, grid, nacc, kNumParams,
                                                          c->d_result, control, s, peers, step,
@@ -1365,14 +1290,9 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
     case kModelScalar: {
       const int grid = residentGrid(c, jac_mode);
       const int nacc = residentDenseRow(c, jac_mode);
-      if (c->scalar_bytes == 8)
-        MOPT_HIP_TRY(mopt::launchScalarModelResident<double>(
-            static_cast<const mopt::ScalarSweepArgs<double> *>(c->d_lm_args), control,
-            c->scalar_model, jac_mode, c->cov_mode, grid, s));
-      else
-        MOPT_HIP_TRY(mopt::launchScalarModelResident<float>(
-            static_cast<const mopt::ScalarSweepArgs<float> *>(c->d_lm_args), control,
-            c->scalar_model, jac_mode, c->cov_mode, grid, s));
+      MOPT_HIP_TRY(mopt::launchScalarModelResident<S>(
+          static_cast<const mopt::ScalarSweepArgs<S> *>(c->d_lm_args), control, c->scalar_model,
+          jac_mode, c->cov_mode, grid, s));
       if (finalize)
         MOPT_HIP_TRY(mopt::launchFinalizeDenseResident(c->d_partials, grid, nacc, n, c->d_result,
                                                      control, s, peers, step, own_index,
@@ -1395,6 +1315,16 @@ int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStrea
     default:
       return fail(MOPT_ERR_UNSUPPORTED, "no resident sweep for this model");
   }
+}
+}  // namespace
+
+int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStream_t s,
+                  unsigned long long base_sequence, const mopt::LmProblem *step, int own_index,
+                  bool finalize) {
+  return withScalar(c->scalar_bytes, [&](auto scalar) {
+    return residentSweepFor<typename decltype(scalar)::type>(c, jac_mode, control, s, base_sequence,
+                                                             step, own_index, finalize);
+  });
 }
 
 void releaseResident(mopt_cost *c) {
@@ -1641,42 +1571,35 @@ int mopt_device_count(int *count) {
 int mopt_se3_from_params(int scalar_bytes, const void *x, void *T_out, void *T_plus_out,
                          void *h_out) {
   if (!x || !T_out) return fail(MOPT_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (scalar_bytes == 8)
-    se3FromParams<double>(static_cast<const double *>(x), static_cast<double *>(T_out),
-                          static_cast<double *>(T_plus_out), static_cast<double *>(h_out));
-  else if (scalar_bytes == 4)
-    se3FromParams<float>(static_cast<const float *>(x), static_cast<float *>(T_out),
-                         static_cast<float *>(T_plus_out), static_cast<float *>(h_out));
-  else
-    return fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
-  return MOPT_OK;
+  const bool known = mopt::dispatch::widthOrFail(scalar_bytes, false, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    se3FromParams<S>(static_cast<const S *>(x), static_cast<S *>(T_out), static_cast<S *>(T_plus_out),
+                     static_cast<S *>(h_out));
+    return true;
+  });
+  return known ? MOPT_OK : fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
 }
 
 int mopt_se3_plus(int scalar_bytes, const void *x, const void *delta, void *x_out) {
   if (!x || !delta || !x_out) return fail(MOPT_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (scalar_bytes == 8)
-    moptimizer::so3::se3Plus<double>(static_cast<const double *>(x),
-                                     static_cast<const double *>(delta), static_cast<double *>(x_out));
-  else if (scalar_bytes == 4)
-    moptimizer::so3::se3Plus<float>(static_cast<const float *>(x), static_cast<const float *>(delta),
-                                    static_cast<float *>(x_out));
-  else
-    return fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
-  return MOPT_OK;
+  const bool known = mopt::dispatch::widthOrFail(scalar_bytes, false, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    moptimizer::so3::se3Plus<S>(static_cast<const S *>(x), static_cast<const S *>(delta),
+                                static_cast<S *>(x_out));
+    return true;
+  });
+  return known ? MOPT_OK : fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
 }
 
 int mopt_se3_plus_right(int scalar_bytes, const void *x, const void *delta, void *x_out) {
   if (!x || !delta || !x_out) return fail(MOPT_ERR_INVALID_ARGUMENT, "NULL argument");
-  if (scalar_bytes == 8)
-    moptimizer::so3::se3PlusRight<double>(static_cast<const double *>(x),
-                                          static_cast<const double *>(delta),
-                                          static_cast<double *>(x_out));
-  else if (scalar_bytes == 4)
-    moptimizer::so3::se3PlusRight<float>(static_cast<const float *>(x),
-                                         static_cast<const float *>(delta), static_cast<float *>(x_out));
-  else
-    return fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
-  return MOPT_OK;
+  const bool known = mopt::dispatch::widthOrFail(scalar_bytes, false, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    moptimizer::so3::se3PlusRight<S>(static_cast<const S *>(x), static_cast<const S *>(delta),
+                                     static_cast<S *>(x_out));
+    return true;
+  });
+  return known ? MOPT_OK : fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 or 8");
 }
 
 int mopt_point2point_create(mopt_cost **out, int device, int scalar_bytes, const void *src_xyz,
@@ -1743,20 +1666,18 @@ int mopt_point2point_set_data(mopt_cost *c, const void *src_xyz, const void *tgt
     const size_t bytes = size_t(count) * 3 * c->scalar_bytes;
     const int rc = stageInputs(src_xyz, bytes, tgt_xyz, bytes, flags, c->stream, st);
     if (rc != MOPT_OK) return rc;
-    if (c->scalar_bytes == 8)
-      MOPT_HIP_TRY(mopt::launchRelayoutP2P<double>(
-          static_cast<const double *>(st.a), static_cast<const double *>(st.b), count,
-          static_cast<double *>(c->d_tiles), c->num_tiles, c->stream));
-    else
-      MOPT_HIP_TRY(mopt::launchRelayoutP2P<float>(
-          static_cast<const float *>(st.a), static_cast<const float *>(st.b), count,
-          static_cast<float *>(c->d_tiles), c->num_tiles, c->stream));
+    MOPT_HIP_TRY(withScalar(c->scalar_bytes, [&](auto scalar) {
+      using S = typename decltype(scalar)::type;
+      return mopt::launchRelayoutP2P<S>(static_cast<const S *>(st.a), static_cast<const S *>(st.b), count,
+                                        static_cast<S *>(c->d_tiles), c->num_tiles, c->stream);
+    }));
     // the scale of the scene (leftBasisCancels, hasSmallForwardStep); d_result is idle: the cost was quiesced
     unsigned long long *d_box = reinterpret_cast<unsigned long long *>(c->d_result);
     unsigned long long box[6];
-    MOPT_HIP_TRY(c->scalar_bytes == 8
-                     ? mopt::launchSourceBox<double>(static_cast<const double *>(c->d_tiles), count, d_box, c->stream)
-                     : mopt::launchSourceBox<float>(static_cast<const float *>(c->d_tiles), count, d_box, c->stream));
+    MOPT_HIP_TRY(withScalar(c->scalar_bytes, [&](auto scalar) {
+      using S = typename decltype(scalar)::type;
+      return mopt::launchSourceBox<S>(static_cast<const S *>(c->d_tiles), count, d_box, c->stream);
+    }));
     MOPT_HIP_TRY(hipMemcpyAsync(box, d_box, sizeof box, hipMemcpyDeviceToHost, c->stream));
     MOPT_HIP_TRY(hipStreamSynchronize(c->stream));
     double diag2 = 0.0, center2 = 0.0;

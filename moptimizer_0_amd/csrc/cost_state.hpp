@@ -44,6 +44,13 @@ constexpr int kMaxParamBytes = mopt::kMaxWideParams * 8;
 constexpr int kResultSlots = 288;
 constexpr int kPartialRowSlots = 96;  // the partial-row buffer is max_grid rows of this many doubles
 
+// f(tag) for a cost's scalar type: `typename decltype(tag)::type` is double or float (scalar_bytes is 8
+// or 4: every create call checks it)
+template <typename F>
+auto withScalar(int scalar_bytes, F &&f) {
+  return mopt::dispatch::widthOrDefault<float>(scalar_bytes, f);
+}
+
 inline int envInt(const char *name, int fallback) {
   const char *v = std::getenv(name);
   if (!v || !*v) return fallback;

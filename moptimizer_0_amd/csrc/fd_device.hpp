@@ -8,6 +8,8 @@
 
 #include "sweep_device.hpp"
 
+#include <cstdlib>
+
 namespace mopt {
 namespace {
 
@@ -97,6 +99,29 @@ enum FdRotationHome : int {
   kFdRotationMixed = 2,
   kFdRotationMixedPlus = 3
 };
+
+// The home by scalar type and covariance form.  fp64: identity / symmetric covariance leave room for
+// the 54 VGPRs (206 / 220 in all: two waves per SIMD either way); the general form (43 accumulators)
+// for 48 of them (256: three entries of the third perturbed rotation re-read from LDS; all from LDS
+// 106 us at 10 M, two rotations in registers 100.5-101.3, this 99.5); fp32 (whose LDS reads are half
+// the size) re-reads everything from LDS.
+template <typename S, int COV>
+constexpr int kFdHomeFor = sizeof(S) == 8 ? (COV != kCovGeneral ? int(kFdRotationRegisters)
+                                                                : int(kFdRotationMixedPlus))
+                                          : int(kFdRotationLds);
+
+// f(tag) for the home the blocking forward-difference sweep of <S, COV> runs with: kFdHomeFor, or what
+// MOPT_FD_ROTATION_HOME=0|1|2|3 names (tuning; any other value: LDS).  The resident forms always take
+// kFdHomeFor.
+template <typename S, int COV, typename F>
+hipError_t withFdRotationHome(F &&f) {
+  static const int forced = [] {
+    const char *e = getenv("MOPT_FD_ROTATION_HOME");
+    return e ? atoi(e) : -1;
+  }();
+  return dispatch::intOrDefault<kFdRotationLds, kFdRotationRegisters, kFdRotationMixed, kFdRotationMixedPlus>(
+      forced >= 0 ? forced : kFdHomeFor<S, COV>, f);
+}
 
 // for_each_pack(body): calls body(packs, first) for every 16-byte pack of correspondences this lane is to
 // evaluate — the ping-pong walk over this workgroup's tiles (p2pForwardDiffBody below), or the tiles a

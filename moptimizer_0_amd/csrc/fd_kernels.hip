@@ -41,12 +41,6 @@ __global__ __launch_bounds__(kBlockThreads) void p2pForwardDiffKernel(const S *t
   p2pForwardDiffBody<S, STREAMING, COV, HOME>(tiles, num_tiles, A, blockIdx.x, gridDim.x, A);
 }
 
-// the rotation entries' home as in launchForwardDiff
-template <typename S, int COV>
-constexpr int kFdHomeFor = sizeof(S) == 8 ? (COV != kCovGeneral ? int(kFdRotationRegisters)
-                                                                : int(kFdRotationMixedPlus))
-                                          : int(kFdRotationLds);
-
 template <typename S, bool STREAMING, int COV>
 __global__ __launch_bounds__(kBlockThreads) void p2pForwardDiffResidentArgsKernel(
     const P2PSweepArgs<S> *__restrict__ d_args, const LmControl *__restrict__ control) {
@@ -105,37 +99,14 @@ __global__ __launch_bounds__(kBlockThreads) void p2pForwardDiffResidentSetKernel
 template <typename S>
 hipError_t launchForwardDiff(const P2PSweepArgs<S> &args, int cov_mode, int grid,
                              const LaunchSite &site) {
-  // fp64: identity / symmetric covariance leave room for the 54 VGPRs (206 / 220 in all: two waves
-  // per SIMD either way); the general form (43 accumulators) for 48 of them (256: three entries of
-  // the third perturbed rotation re-read from LDS; all from LDS 106 us at 10 M, two rotations in
-  // registers 100.5-101.3, this 99.5); fp32 (whose LDS reads are half the size) re-reads everything
-  // from LDS.  MOPT_FD_ROTATION_HOME=0|1|2|3 overrides (tuning).
-  static const int forced = [] {
-    const char *e = getenv("MOPT_FD_ROTATION_HOME");
-    return e ? atoi(e) : -1;
-  }();
-  const int by_form = sizeof(S) == 8 ? (cov_mode != kCovGeneral ? int(kFdRotationRegisters)
-                                                                : int(kFdRotationMixedPlus))
-                                     : int(kFdRotationLds);
-  const int home = forced >= 0 ? forced : by_form;
-#define MOPT_LAUNCH_FD_HOME(COV, HOME)                                                        \
-  (site.streaming ? launchTiled(p2pForwardDiffKernel<S, true, COV, HOME>, grid, site, args)      \
-                  : launchTiled(p2pForwardDiffKernel<S, false, COV, HOME>, grid, site, args))
-#define MOPT_LAUNCH_FD(COV)                                                                      \
-  (home == kFdRotationRegisters ? MOPT_LAUNCH_FD_HOME(COV, kFdRotationRegisters)                 \
-   : home == kFdRotationMixed   ? MOPT_LAUNCH_FD_HOME(COV, kFdRotationMixed)                     \
-   : home == kFdRotationMixedPlus ? MOPT_LAUNCH_FD_HOME(COV, kFdRotationMixedPlus)               \
-                                : MOPT_LAUNCH_FD_HOME(COV, kFdRotationLds))
-  switch (cov_mode) {
-    case kCovIdentity:
-      return MOPT_LAUNCH_FD(kCovIdentity);
-    case kCovSymmetric:
-      return MOPT_LAUNCH_FD(kCovSymmetric);
-    default:
-      return MOPT_LAUNCH_FD(kCovGeneral);
-  }
-#undef MOPT_LAUNCH_FD
-#undef MOPT_LAUNCH_FD_HOME
+  return withCov(cov_mode, [&](auto cov) {
+    return withFdRotationHome<S, cov()>([&](auto home) {
+      return dispatch::byBool(site.streaming, [&](auto streaming) {
+        return launchBlocking(p2pForwardDiffKernel<S, streaming(), cov(), home()>, grid, site,
+                              args.tiles, args.num_tiles, args);
+      });
+    });
+  });
 }
 template hipError_t launchForwardDiff<float>(const P2PSweepArgs<float> &, int, int, const LaunchSite &);
 template hipError_t launchForwardDiff<double>(const P2PSweepArgs<double> &, int, int,
@@ -145,53 +116,23 @@ template <typename S>
 hipError_t launchForwardDiffResident(const P2PSweepArgs<S> *d_args, const LmControl *control,
                                      int cov_mode, int grid, const LaunchSite &site) {
   // tiles / num_tiles are not in reach of this signature: read through the argument block
-  const dim3 g(grid), b(kBlockThreads);
-#define MOPT_LAUNCH_FD_RESIDENT(COV)                                                              \
-  if (site.streaming)                                                                             \
-    hipLaunchKernelGGL((p2pForwardDiffResidentArgsKernel<S, true, COV>), g, b, 0, site.stream,    \
-                       d_args, control);                                                          \
-  else                                                                                            \
-    hipLaunchKernelGGL((p2pForwardDiffResidentArgsKernel<S, false, COV>), g, b, 0, site.stream,   \
-                       d_args, control)
-  switch (cov_mode) {
-    case kCovIdentity:
-      MOPT_LAUNCH_FD_RESIDENT(kCovIdentity);
-      break;
-    case kCovSymmetric:
-      MOPT_LAUNCH_FD_RESIDENT(kCovSymmetric);
-      break;
-    default:
-      MOPT_LAUNCH_FD_RESIDENT(kCovGeneral);
-      break;
-  }
-#undef MOPT_LAUNCH_FD_RESIDENT
-  return hipGetLastError();
+  return withCov(cov_mode, [&](auto cov) {
+    return dispatch::byBool(site.streaming, [&](auto streaming) {
+      return launchResident(p2pForwardDiffResidentArgsKernel<S, streaming(), cov()>, grid, site.stream,
+                            d_args, control);
+    });
+  });
 }
 template <typename S>
 hipError_t launchForwardDiffEitherResident(const S *tiles, int num_tiles, const P2PSweepArgs<S> *d_args,
                                            const LmControl *control, int cov_mode, int grid,
                                            int moments_grid, const LaunchSite &site) {
-  const dim3 g(grid), b(kBlockThreads);
-#define MOPT_LAUNCH_FD_EITHER(COV)                                                                \
-  if (site.streaming)                                                                             \
-    hipLaunchKernelGGL((p2pForwardDiffEitherResidentKernel<S, true, COV>), g, b, 0, site.stream,  \
-                       tiles, num_tiles, d_args, control, moments_grid);                          \
-  else                                                                                            \
-    hipLaunchKernelGGL((p2pForwardDiffEitherResidentKernel<S, false, COV>), g, b, 0, site.stream, \
-                       tiles, num_tiles, d_args, control, moments_grid)
-  switch (cov_mode) {
-    case kCovIdentity:
-      MOPT_LAUNCH_FD_EITHER(kCovIdentity);
-      break;
-    case kCovSymmetric:
-      MOPT_LAUNCH_FD_EITHER(kCovSymmetric);
-      break;
-    default:
-      MOPT_LAUNCH_FD_EITHER(kCovGeneral);
-      break;
-  }
-#undef MOPT_LAUNCH_FD_EITHER
-  return hipGetLastError();
+  return withCov(cov_mode, [&](auto cov) {
+    return dispatch::byBool(site.streaming, [&](auto streaming) {
+      return launchResident(p2pForwardDiffEitherResidentKernel<S, streaming(), cov()>, grid,
+                            site.stream, tiles, num_tiles, d_args, control, moments_grid);
+    });
+  });
 }
 template hipError_t launchForwardDiffEitherResident<float>(const float *, int, const P2PSweepArgs<float> *,
                                                            const LmControl *, int, int, int,
@@ -203,27 +144,12 @@ template hipError_t launchForwardDiffEitherResident<double>(const double *, int,
 template <typename S>
 hipError_t launchForwardDiffResidentSet(const ResidentSweepSet &set, const LmControl *control,
                                         int cov_mode, const LaunchSite &site) {
-  const dim3 g(set.first_block[set.num_costs]), b(kBlockThreads);
-#define MOPT_LAUNCH_FD_SET(COV)                                                                   \
-  if (site.streaming)                                                                             \
-    hipLaunchKernelGGL((p2pForwardDiffResidentSetKernel<S, true, COV>), g, b, 0, site.stream, set, \
-                       control);                                                                  \
-  else                                                                                            \
-    hipLaunchKernelGGL((p2pForwardDiffResidentSetKernel<S, false, COV>), g, b, 0, site.stream,    \
-                       set, control)
-  switch (cov_mode) {
-    case kCovIdentity:
-      MOPT_LAUNCH_FD_SET(kCovIdentity);
-      break;
-    case kCovSymmetric:
-      MOPT_LAUNCH_FD_SET(kCovSymmetric);
-      break;
-    default:
-      MOPT_LAUNCH_FD_SET(kCovGeneral);
-      break;
-  }
-#undef MOPT_LAUNCH_FD_SET
-  return hipGetLastError();
+  return withCov(cov_mode, [&](auto cov) {
+    return dispatch::byBool(site.streaming, [&](auto streaming) {
+      return launchResident(p2pForwardDiffResidentSetKernel<S, streaming(), cov()>,
+                            set.first_block[set.num_costs], site.stream, set, control);
+    });
+  });
 }
 template hipError_t launchForwardDiffResidentSet<float>(const ResidentSweepSet &, const LmControl *,
                                                         int, const LaunchSite &);

@@ -241,13 +241,11 @@ int mopt_icp_create_from(mopt_cost **out, int device, int scalar_bytes, const vo
   hipStream_t build_stream = nullptr;
   MOPT_HIP_TRY(acquireStream(device, &build_stream));
   DeviceScratch d_src_sorted(build_stream);  // (read once more by the cost's own stream, which the create call synchronises)
-  int rc = scalar_bytes == 8
-               ? buildIcpGrid<double>(static_cast<const double *>(src_xyz), num_src,
-                                      static_cast<const double *>(tgt_xyz), num_tgt, max_distance,
-                                      flags, build_stream, matcher, d_src_sorted)
-               : buildIcpGrid<float>(static_cast<const float *>(src_xyz), num_src,
-                                     static_cast<const float *>(tgt_xyz), num_tgt, max_distance,
-                                     flags, build_stream, matcher, d_src_sorted);
+  int rc = withScalar(scalar_bytes, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    return buildIcpGrid<S>(static_cast<const S *>(src_xyz), num_src, static_cast<const S *>(tgt_xyz), num_tgt,
+                           max_distance, flags, build_stream, matcher, d_src_sorted);
+  });
   (void)hipStreamSynchronize(build_stream);
   releaseStream(device, build_stream);
   // the sources go into the resident tiles in cell order; the target planes are filled by the
@@ -278,8 +276,10 @@ int mopt_icp_update(mopt_cost *c, const void *x, int64_t *num_matched) {
   if (!c || !x) return fail(MOPT_ERR_INVALID_ARGUMENT, "NULL argument");
   if (!c->matcher) return fail(MOPT_ERR_INVALID_ARGUMENT, "not a cost made by mopt_icp_create");
   MOPT_HIP_TRY(hipSetDevice(c->device));
-  return c->scalar_bytes == 8 ? icpUpdate<double>(c, static_cast<const double *>(x), num_matched)
-                              : icpUpdate<float>(c, static_cast<const float *>(x), num_matched);
+  return withScalar(c->scalar_bytes, [&](auto scalar) {
+    using S = typename decltype(scalar)::type;
+    return icpUpdate<S>(c, static_cast<const S *>(x), num_matched);
+  });
 }
 
 int mopt_icp_grid(const mopt_cost *c, double *cell_edge, int *reach, int dims[3], double origin[3]) {
@@ -309,11 +309,11 @@ int mopt_icp_get_matches(mopt_cost *c, void *tgt_out_xyz) {
   MOPT_HIP_TRY(deviceAlloc(&d_tmp, bytes));
   hipError_t e = order ? hipMemsetAsync(d_tmp, 0xff, bytes, c->stream) : hipSuccess;
   if (e == hipSuccess)
-    e = c->scalar_bytes == 8
-            ? mopt::launchGatherTargets<double>(static_cast<const double *>(c->d_tiles), c->count, order,
-                                                static_cast<double *>(d_tmp), c->stream)
-            : mopt::launchGatherTargets<float>(static_cast<const float *>(c->d_tiles), c->count, order,
-                                               static_cast<float *>(d_tmp), c->stream);
+    e = withScalar(c->scalar_bytes, [&](auto scalar) {
+      using S = typename decltype(scalar)::type;
+      return mopt::launchGatherTargets<S>(static_cast<const S *>(c->d_tiles), c->count, order,
+                                          static_cast<S *>(d_tmp), c->stream);
+    });
   if (e == hipSuccess) e = hipMemcpyAsync(tgt_out_xyz, d_tmp, bytes, hipMemcpyDeviceToHost, c->stream);
   const hipError_t synced = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = synced;

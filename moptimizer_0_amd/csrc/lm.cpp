@@ -201,21 +201,19 @@ int mopt_lm_minimize(mopt_cost *const *costs, int num_costs, const int *jacobian
                              problem.n == kNumParams && lead->num_tiles >= 1 &&
                              lead->num_tiles <= small_tiles &&
                              max_points <= 4096;  // (one kernel for the whole loop: at ~8 us a point, <= 35 ms)
-  if (one_workgroup) {
-    if (lead->scalar_bytes == 8)
-      MOPT_HIP_TRY(mopt::launchP2PSolveSmall<double>(
-          static_cast<const double *>(lead->d_tiles), lead->num_tiles,
-          static_cast<const mopt::P2PSweepArgs<double> *>(lead->d_lm_args), lead->d_lm_basis,
-          lead->d_result, problem, static_cast<const double *>(x), int(max_points), lead->cov_mode, s));
-    else
-      MOPT_HIP_TRY(mopt::launchP2PSolveSmall<float>(
-          static_cast<const float *>(lead->d_tiles), lead->num_tiles,
-          static_cast<const mopt::P2PSweepArgs<float> *>(lead->d_lm_args), lead->d_lm_basis,
-          lead->d_result, problem, static_cast<const float *>(x), int(max_points), lead->cov_mode, s));
-  } else if (lead->scalar_bytes == 8)
-    MOPT_HIP_TRY(mopt::launchLmStep<double>(problem, true, static_cast<const double *>(x), s));
+  if (one_workgroup)
+    MOPT_HIP_TRY(withScalar(lead->scalar_bytes, [&](auto scalar) {
+      using S = typename decltype(scalar)::type;
+      return mopt::launchP2PSolveSmall<S>(
+          static_cast<const S *>(lead->d_tiles), lead->num_tiles,
+          static_cast<const mopt::P2PSweepArgs<S> *>(lead->d_lm_args), lead->d_lm_basis, lead->d_result,
+          problem, static_cast<const S *>(x), int(max_points), lead->cov_mode, s);
+    }));
   else
-    MOPT_HIP_TRY(mopt::launchLmStep<float>(problem, true, static_cast<const float *>(x), s));
+    MOPT_HIP_TRY(withScalar(lead->scalar_bytes, [&](auto scalar) {
+      using S = typename decltype(scalar)::type;
+      return mopt::launchLmStep<S>(problem, true, static_cast<const S *>(x), s);
+    }));
 
   // One sweep per evaluated point: the linearization at x0, then at most lm_max_iterations trial
   // points per outer iteration.  The host stays `window` points ahead of the device; whatever is

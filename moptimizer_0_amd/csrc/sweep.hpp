@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include "aql.hpp"
+#include "dispatch.hpp"
 
 #include <cstdint>
 
@@ -44,6 +45,42 @@ constexpr int kAccFull = 36 + 6 + 1;  // full H (non-symmetric covariance) | b |
 constexpr int kAccMoments = 23;       // w | w p (3) | w p p^T (6) | w r (3) | w p r^T (9) | r^T r
 constexpr int kAccCost = 1;
 constexpr int kResultDoubles = kNumParams * kNumParams + kNumParams + 1;  // 43
+// Values of a workgroup's dense partial row: H (whole under a general covariance, else its upper
+// triangle) | b | sum_sq — for a model of n parameters, and for the six-parameter costs.
+constexpr int denseRowLength(int n, int cov_mode) {
+  return (cov_mode == kCovGeneral ? n * n : n * (n + 1) / 2) + n + 1;
+}
+constexpr int denseRowLength(int cov_mode) { return denseRowLength(kNumParams, cov_mode); }
+static_assert(denseRowLength(kCovGeneral) == kAccFull && denseRowLength(kCovSymmetric) == kAccSym &&
+                  denseRowLength(kCovIdentity) == kAccSym,
+              "the six-parameter rows");
+
+// ---- run-time word -> template argument (dispatch.hpp) ----------------------------------------
+// f(tag): `tag()` is the enumerator as a constant expression.
+// Covariance form: identity, symmetric, anything else general.
+template <typename F>
+auto withCov(int cov_mode, F &&f) {
+  return dispatch::intOrDefault<kCovGeneral, kCovIdentity, kCovSymmetric>(cov_mode, f);
+}
+// Analytic Jacobian of the point2point cost (kJacNumeric goes to the forward-difference launchers
+// before this is asked); an unknown mode is hipErrorInvalidValue.
+template <typename F>
+hipError_t withP2PAnalyticJac(int jac_mode, F &&f) {
+  return dispatch::intOrFail<kJacAnalytic, kJacAnalyticTst, kJacAnalyticLeft, kJacAnalyticRight>(
+      jac_mode, hipErrorInvalidValue, f);
+}
+// Jacobian of the generic models (scalar, run-time compiled): forward differences or the model's own.
+template <typename F>
+auto withModelJac(int jac_mode, F &&f) {
+  return dispatch::intOrDefault<kJacAnalytic, kJacNumeric>(jac_mode, f);
+}
+// The scalar type of the LM step a resident finalize kernel takes in the same launch: none (0) without
+// a `step`, else 8 or 4 bytes.
+template <typename F>
+auto withLmStepScalar(bool step, int scalar_bytes, F &&f) {
+  if (!step) return f(dispatch::Int<0>{});
+  return dispatch::intOrDefault<4, 8>(scalar_bytes, f);
+}
 
 // Per-sweep constants, passed by value as the kernel argument.
 template <typename S>

@@ -258,23 +258,59 @@ __device__ __forceinline__ int costOfBlock(const ResidentSweepSet &set) {
   return k;
 }
 
-// moments / cost / forward-difference sweeps: (tiles, num_tiles, args) signature (the leading scalar
-// arguments are preloaded into SGPRs at wave launch); optionally a timestamped dispatch
-template <typename Kernel, typename S>
-hipError_t launchTiled(Kernel kernel, int grid, const LaunchSite &site, const P2PSweepArgs<S> &args) {
+// ---- host-side launch helpers ---------------------------------------------------------------------
+// A blocking call's sweep: the cost's own queue where the site offers one (aql.hpp), else the HIP
+// stream, its dispatch timestamped when the site carries events.  The moments / cost / forward-
+// difference sweeps pass (args.tiles, args.num_tiles, args): the leading scalar arguments are
+// preloaded into SGPRs at wave launch.
+template <typename Kernel, typename... Args>
+hipError_t launchBlocking(Kernel kernel, int grid, const LaunchSite &site, const Args &...args) {
   if (site.aql.queue && site.aql_used && !site.time_start &&
-      mopt_detail::aqlLaunch(site.aql, kernel, uint32_t(grid), uint32_t(kBlockThreads), args.tiles,
-                             args.num_tiles, args)) {
+      mopt_detail::aqlLaunch(site.aql, kernel, uint32_t(grid), uint32_t(kBlockThreads), args...)) {
     *site.aql_used = true;
     return hipSuccess;
   }
   if (site.time_start && site.time_stop)
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, site.stream, site.time_start,
-                          site.time_stop, 0, args.tiles, args.num_tiles, args);
+                          site.time_stop, 0, args...);
   else
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, site.stream, args.tiles,
-                       args.num_tiles, args);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, site.stream, args...);
   return hipGetLastError();
+}
+
+// A sweep of the device-resident loop: always the HIP stream.
+template <typename Kernel, typename... Args>
+hipError_t launchResident(Kernel kernel, int grid, hipStream_t stream, const Args &...args) {
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, stream, args...);
+  return hipGetLastError();
+}
+
+// Built-in scalar models (sweep_kernels.hip) as tags: f(ScalarModel<ModelT>{}), to be taken by a
+// function template that deduces ModelT; an unknown kind is hipErrorInvalidValue.
+template <typename S> struct ExpCurve;
+template <typename S> struct Rational;
+template <typename S> struct Powell;
+template <typename S> struct ExpCurveMarked;
+template <typename S> struct RationalMarked;
+template <template <typename> class ModelT>
+struct ScalarModel {};
+
+template <typename F>
+hipError_t withScalarModel(int kind, F &&f) {
+  switch (kind) {
+    case kScalarExpCurve:
+      return f(ScalarModel<ExpCurve>{});
+    case kScalarRational:
+      return f(ScalarModel<Rational>{});
+    case kScalarPowell:
+      return f(ScalarModel<Powell>{});
+    case kScalarExpCurveMarked:
+      return f(ScalarModel<ExpCurveMarked>{});
+    case kScalarRationalMarked:
+      return f(ScalarModel<RationalMarked>{});
+    default:
+      return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace

@@ -1753,58 +1753,18 @@ hipError_t launchRelayoutReproj(const double *points_xyzw, const int32_t *pixels
   return hipGetLastError();
 }
 
-namespace {
-template <typename Kernel, typename Args>
-hipError_t launchSweep(Kernel kernel, int grid, const LaunchSite &site, const Args &args) {
-  if (site.aql.queue && site.aql_used && !site.time_start &&
-      mopt_detail::aqlLaunch(site.aql, kernel, uint32_t(grid), uint32_t(kBlockThreads), args)) {
-    *site.aql_used = true;
-    return hipSuccess;
-  }
-  if (site.time_start && site.time_stop)
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, site.stream, site.time_start,
-                          site.time_stop, 0, args);
-  else
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlockThreads), 0, site.stream, args);
-  return hipGetLastError();
-}
-
-template <typename S, int JAC>
-hipError_t launchLiteralCov(const P2PSweepArgs<S> &args, int cov_mode, int grid,
-                            const LaunchSite &site) {
-#define MOPT_LAUNCH_LITERAL(COV)                                                                   \
-  (site.streaming ? launchTiled(p2pLinearizeLiteralKernel<S, JAC, COV, true>, grid, site, args)   \
-                  : launchTiled(p2pLinearizeLiteralKernel<S, JAC, COV, false>, grid, site, args))
-  switch (cov_mode) {
-    case kCovIdentity:
-      return MOPT_LAUNCH_LITERAL(kCovIdentity);
-    case kCovSymmetric:
-      return MOPT_LAUNCH_LITERAL(kCovSymmetric);
-    default:
-      return MOPT_LAUNCH_LITERAL(kCovGeneral);
-  }
-#undef MOPT_LAUNCH_LITERAL
-}
-
-}  // namespace
-
 template <typename S>
 hipError_t launchP2PLinearizeLiteral(const P2PSweepArgs<S> &args, int jac_mode, int cov_mode,
                                      int grid, const LaunchSite &site) {
-  switch (jac_mode) {
-    case kJacAnalytic:
-      return launchLiteralCov<S, kJacAnalytic>(args, cov_mode, grid, site);
-    case kJacAnalyticTst:
-      return launchLiteralCov<S, kJacAnalyticTst>(args, cov_mode, grid, site);
-    case kJacNumeric:
-      return launchForwardDiff<S>(args, cov_mode, grid, site);
-    case kJacAnalyticLeft:
-      return launchLiteralCov<S, kJacAnalyticLeft>(args, cov_mode, grid, site);
-    case kJacAnalyticRight:
-      return launchLiteralCov<S, kJacAnalyticRight>(args, cov_mode, grid, site);
-    default:
-      return hipErrorInvalidValue;
-  }
+  if (jac_mode == kJacNumeric) return launchForwardDiff<S>(args, cov_mode, grid, site);
+  return withP2PAnalyticJac(jac_mode, [&](auto jac) {
+    return withCov(cov_mode, [&](auto cov) {
+      return dispatch::byBool(site.streaming, [&](auto streaming) {
+        return launchBlocking(p2pLinearizeLiteralKernel<S, jac(), cov(), streaming()>, grid, site,
+                              args.tiles, args.num_tiles, args);
+      });
+    });
+  });
 }
 template hipError_t launchP2PLinearizeLiteral<float>(const P2PSweepArgs<float> &, int, int, int,
                                                      const LaunchSite &);
@@ -1813,8 +1773,9 @@ template hipError_t launchP2PLinearizeLiteral<double>(const P2PSweepArgs<double>
 
 template <typename S>
 hipError_t launchP2PMoments(const P2PSweepArgs<S> &args, int grid, const LaunchSite &site) {
-  return site.streaming ? launchTiled(p2pMomentsKernel<S, true>, grid, site, args)
-                        : launchTiled(p2pMomentsKernel<S, false>, grid, site, args);
+  return dispatch::byBool(site.streaming, [&](auto streaming) {
+    return launchBlocking(p2pMomentsKernel<S, streaming()>, grid, site, args.tiles, args.num_tiles, args);
+  });
 }
 template hipError_t launchP2PMoments<float>(const P2PSweepArgs<float> &, int, const LaunchSite &);
 template hipError_t launchP2PMoments<double>(const P2PSweepArgs<double> &, int,
@@ -1822,26 +1783,22 @@ template hipError_t launchP2PMoments<double>(const P2PSweepArgs<double> &, int,
 
 template <typename S>
 hipError_t launchP2PCost(const P2PSweepArgs<S> &args, int grid, const LaunchSite &site) {
-  return site.streaming ? launchTiled(p2pCostKernel<S, true>, grid, site, args)
-                        : launchTiled(p2pCostKernel<S, false>, grid, site, args);
+  return dispatch::byBool(site.streaming, [&](auto streaming) {
+    return launchBlocking(p2pCostKernel<S, streaming()>, grid, site, args.tiles, args.num_tiles, args);
+  });
 }
 template hipError_t launchP2PCost<float>(const P2PSweepArgs<float> &, int, const LaunchSite &);
 template hipError_t launchP2PCost<double>(const P2PSweepArgs<double> &, int, const LaunchSite &);
 
 hipError_t launchReprojLinearize(const ReprojSweepArgs &args, int cov_mode, int grid,
                                  const LaunchSite &site) {
-  switch (cov_mode) {
-    case kCovIdentity:
-      return launchSweep(reprojKernel<kCovIdentity, false>, grid, site, args);
-    case kCovSymmetric:
-      return launchSweep(reprojKernel<kCovSymmetric, false>, grid, site, args);
-    default:
-      return launchSweep(reprojKernel<kCovGeneral, false>, grid, site, args);
-  }
+  return withCov(cov_mode, [&](auto cov) {
+    return launchBlocking(reprojKernel<cov(), false>, grid, site, args);
+  });
 }
 
 hipError_t launchReprojCost(const ReprojSweepArgs &args, int grid, const LaunchSite &site) {
-  return launchSweep(reprojKernel<kCovIdentity, true>, grid, site, args);
+  return launchBlocking(reprojKernel<kCovIdentity, true>, grid, site, args);
 }
 
 bool aqlFinalizersLoaded(const mopt_detail::AqlSite &site) {
@@ -1851,89 +1808,69 @@ bool aqlFinalizersLoaded(const mopt_detail::AqlSite &site) {
          mopt_detail::aqlLookup(site.device, reinterpret_cast<const void *>(finalizeCostKernel));
 }
 
+namespace {
+// A blocking call's finalize kernel (one workgroup; its last two parameters are the hand-over to the
+// host and the sum over the ranks): to the queue its sweep went to, when that was the cost's own —
+// the three kernels are looked up beforehand (aqlFinalizersLoaded), so that cannot fail over — else
+// to the stream.
+template <typename Kernel, typename... Args>
+hipError_t launchFinalize(Kernel kernel, const HostPublish &pub, hipStream_t stream,
+                          const PeerCombine *peers, const mopt_detail::AqlSite *aql,
+                          const Args &...args) {
+  const PeerCombine pc = peers ? *peers : PeerCombine();
+  if (aql)
+    return mopt_detail::aqlLaunch(*aql, kernel, 1u, uint32_t(kFinalThreads), args..., pub, pc)
+               ? hipSuccess
+               : hipErrorLaunchFailure;
+  hipLaunchKernelGGL(kernel, dim3(1), dim3(kFinalThreads), 0, stream, args..., pub, pc);
+  return hipGetLastError();
+}
+
+bool isDenseRow(int nacc, int n) {
+  return nacc == denseRowLength(n, kCovSymmetric) || nacc == denseRowLength(n, kCovGeneral);
+}
+}  // namespace
+
 hipError_t launchFinalizeDense(const double *partials, int grid, int nacc, int n, double *result,
                                const HostPublish &pub, hipStream_t stream,
                                const PeerCombine *peers, const mopt_detail::AqlSite *aql) {
-  if (n < 1 || n > kMaxWideParams || (nacc != n * (n + 1) / 2 + n + 1 && nacc != n * n + n + 1))
-    return hipErrorInvalidValue;
+  if (n < 1 || n > kMaxWideParams || !isDenseRow(nacc, n)) return hipErrorInvalidValue;
   if (peers && peers->num_ranks > 0 && n * n + n + 1 > kSlotData) return hipErrorInvalidValue;
-  if (aql)  // the sweep went to this queue: so must its finalize (looked up beforehand)
-    return mopt_detail::aqlLaunch(*aql, finalizeDenseKernel, 1u, uint32_t(kFinalThreads), partials, grid,
-                                  nacc, n, result, pub, peers ? *peers : PeerCombine())
-               ? hipSuccess
-               : hipErrorLaunchFailure;
-  hipLaunchKernelGGL(finalizeDenseKernel, dim3(1), dim3(kFinalThreads), 0, stream, partials, grid,
-                     nacc, n, result, pub, peers ? *peers : PeerCombine());
-  return hipGetLastError();
+  return launchFinalize(finalizeDenseKernel, pub, stream, peers, aql, partials, grid, nacc, n, result);
 }
 
 hipError_t launchFinalizeMoments(const double *partials, int grid, const AffineBasis &basis,
                                  double *result, const HostPublish &pub, hipStream_t stream,
                                  const PeerCombine *peers, const mopt_detail::AqlSite *aql) {
-  if (aql)
-    return mopt_detail::aqlLaunch(*aql, finalizeMomentsKernel, 1u, uint32_t(kFinalThreads), partials, grid,
-                                  basis, result, pub, peers ? *peers : PeerCombine())
-               ? hipSuccess
-               : hipErrorLaunchFailure;
-  hipLaunchKernelGGL(finalizeMomentsKernel, dim3(1), dim3(kFinalThreads), 0, stream, partials,
-                     grid, basis, result, pub, peers ? *peers : PeerCombine());
-  return hipGetLastError();
+  return launchFinalize(finalizeMomentsKernel, pub, stream, peers, aql, partials, grid, basis, result);
 }
 
 hipError_t launchFinalizeCost(const double *partials, int grid, double *result,
                               const HostPublish &pub, hipStream_t stream,
                               const PeerCombine *peers, const mopt_detail::AqlSite *aql) {
-  if (aql)
-    return mopt_detail::aqlLaunch(*aql, finalizeCostKernel, 1u, uint32_t(kFinalThreads), partials, grid,
-                                  result, pub, peers ? *peers : PeerCombine())
-               ? hipSuccess
-               : hipErrorLaunchFailure;
-  hipLaunchKernelGGL(finalizeCostKernel, dim3(1), dim3(kFinalThreads), 0, stream, partials, grid,
-                     result, pub, peers ? *peers : PeerCombine());
-  return hipGetLastError();
+  return launchFinalize(finalizeCostKernel, pub, stream, peers, aql, partials, grid, result);
 }
 
 namespace {
 template <typename S, template <typename> class ModelT>
-hipError_t launchScalarFor(const ScalarSweepArgs<S> &args, bool cost_only, int jac_mode,
-                           int cov_mode, int grid, const LaunchSite &site) {
+hipError_t launchScalarFor(ScalarModel<ModelT>, const ScalarSweepArgs<S> &args, bool cost_only,
+                           int jac_mode, int cov_mode, int grid, const LaunchSite &site) {
   if (cost_only)
-    return launchSweep(scalarModelKernel<S, ModelT, kJacNumeric, kCovIdentity, true>, grid, site, args);
-  const bool numeric = (jac_mode == kJacNumeric);
-#define MOPT_LAUNCH_SCALAR(JAC, COV) \
-  return launchSweep(scalarModelKernel<S, ModelT, JAC, COV, false>, grid, site, args)
-  switch (cov_mode) {
-    case kCovIdentity:
-      if (numeric) MOPT_LAUNCH_SCALAR(kJacNumeric, kCovIdentity);
-      else MOPT_LAUNCH_SCALAR(kJacAnalytic, kCovIdentity);
-    case kCovSymmetric:
-      if (numeric) MOPT_LAUNCH_SCALAR(kJacNumeric, kCovSymmetric);
-      else MOPT_LAUNCH_SCALAR(kJacAnalytic, kCovSymmetric);
-    default:
-      if (numeric) MOPT_LAUNCH_SCALAR(kJacNumeric, kCovGeneral);
-      else MOPT_LAUNCH_SCALAR(kJacAnalytic, kCovGeneral);
-  }
-#undef MOPT_LAUNCH_SCALAR
+    return launchBlocking(scalarModelKernel<S, ModelT, kJacNumeric, kCovIdentity, true>, grid, site, args);
+  return withCov(cov_mode, [&](auto cov) {
+    return withModelJac(jac_mode, [&](auto jac) {
+      return launchBlocking(scalarModelKernel<S, ModelT, jac(), cov(), false>, grid, site, args);
+    });
+  });
 }
 }  // namespace
 
 template <typename S>
 hipError_t launchScalarModel(const ScalarSweepArgs<S> &args, int model, bool cost_only,
                              int jac_mode, int cov_mode, int grid, const LaunchSite &site) {
-  switch (model) {
-    case kScalarExpCurve:
-      return launchScalarFor<S, ExpCurve>(args, cost_only, jac_mode, cov_mode, grid, site);
-    case kScalarRational:
-      return launchScalarFor<S, Rational>(args, cost_only, jac_mode, cov_mode, grid, site);
-    case kScalarPowell:
-      return launchScalarFor<S, Powell>(args, cost_only, jac_mode, cov_mode, grid, site);
-    case kScalarExpCurveMarked:
-      return launchScalarFor<S, ExpCurveMarked>(args, cost_only, jac_mode, cov_mode, grid, site);
-    case kScalarRationalMarked:
-      return launchScalarFor<S, RationalMarked>(args, cost_only, jac_mode, cov_mode, grid, site);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return withScalarModel(model, [&](auto kind) {
+    return launchScalarFor<S>(kind, args, cost_only, jac_mode, cov_mode, grid, site);
+  });
 }
 template hipError_t launchScalarModel<float>(const ScalarSweepArgs<float> &, int, bool, int, int,
                                              int, const LaunchSite &);
@@ -2056,27 +1993,16 @@ hipError_t launchP2PSolveSmall(const S *tiles, int num_tiles, const P2PSweepArgs
     return hipErrorInvalidValue;
   LmStart<S> start;
   for (int i = 0; i < kMaxWideParams; ++i) start.x[i] = i < problem.n ? x0[i] : S(0);
-  const dim3 g(1), b(kBlockThreads);
-  switch (problem.fd_per_iterate ? fd_cov : -1) {
-    case kCovIdentity:
-      hipLaunchKernelGGL((p2pSolveSmallKernel<S, kCovIdentity>), g, b, 0, stream, tiles, num_tiles, d_args,
-                         d_basis, result, problem, start, max_points);
-      break;
-    case kCovSymmetric:
-      hipLaunchKernelGGL((p2pSolveSmallKernel<S, kCovSymmetric>), g, b, 0, stream, tiles, num_tiles, d_args,
-                         d_basis, result, problem, start, max_points);
-      break;
-    case kCovGeneral:
-      hipLaunchKernelGGL((p2pSolveSmallKernel<S, kCovGeneral>), g, b, 0, stream, tiles, num_tiles, d_args,
-                         d_basis, result, problem, start, max_points);
-      break;
-    default:
-      if (problem.fd_per_iterate) return hipErrorInvalidValue;  // (needs the literal form: name its covariance)
-      hipLaunchKernelGGL((p2pSolveSmallKernel<S, -1>), g, b, 0, stream, tiles, num_tiles, d_args, d_basis,
-                         result, problem, start, max_points);
-      break;
-  }
-  return hipGetLastError();
+  // FD_COV: the covariance form of the literal forward-difference sweep the kernel holds next to the
+  // moments where the step chooses per point (there it must be named); -1: the moments alone
+  auto launch = [&](auto fd) {
+    return launchResident(p2pSolveSmallKernel<S, fd()>, 1, stream, tiles, num_tiles, d_args, d_basis,
+                          result, problem, start, max_points);
+  };
+  if (problem.fd_per_iterate)
+    return dispatch::intOrFail<kCovIdentity, kCovSymmetric, kCovGeneral>(fd_cov, hipErrorInvalidValue,
+                                                                         launch);
+  return launch(dispatch::Int<-1>{});
 }
 template hipError_t launchP2PSolveSmall<float>(const float *, int, const P2PSweepArgs<float> *,
                                                const AffineBasis *, double *, const LmProblem &,
@@ -2088,13 +2014,10 @@ template hipError_t launchP2PSolveSmall<double>(const double *, int, const P2PSw
 template <typename S>
 hipError_t launchP2PMomentsResident(const S *tiles, int num_tiles, const P2PSweepArgs<S> *d_args,
                                     const LmControl *control, int grid, const LaunchSite &site) {
-  if (site.streaming)
-    hipLaunchKernelGGL((p2pMomentsResidentKernel<S, true>), dim3(grid), dim3(kBlockThreads), 0,
-                       site.stream, tiles, num_tiles, d_args, control);
-  else
-    hipLaunchKernelGGL((p2pMomentsResidentKernel<S, false>), dim3(grid), dim3(kBlockThreads), 0,
-                       site.stream, tiles, num_tiles, d_args, control);
-  return hipGetLastError();
+  return dispatch::byBool(site.streaming, [&](auto streaming) {
+    return launchResident(p2pMomentsResidentKernel<S, streaming()>, grid, site.stream, tiles, num_tiles,
+                          d_args, control);
+  });
 }
 template hipError_t launchP2PMomentsResident<float>(const float *, int, const P2PSweepArgs<float> *,
                                                     const LmControl *, int, const LaunchSite &);
@@ -2102,46 +2025,17 @@ template hipError_t launchP2PMomentsResident<double>(const double *, int,
                                                      const P2PSweepArgs<double> *,
                                                      const LmControl *, int, const LaunchSite &);
 
-namespace {
-template <typename S, int JAC>
-hipError_t launchLiteralResidentCov(const P2PSweepArgs<S> *d_args, const LmControl *control,
-                                    int cov_mode, int grid, const LaunchSite &site) {
-  const dim3 g(grid), b(kBlockThreads);
-  switch (cov_mode) {
-    case kCovIdentity:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentKernel<S, JAC, kCovIdentity>), g, b, 0,
-                         site.stream, d_args, control);
-      break;
-    case kCovSymmetric:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentKernel<S, JAC, kCovSymmetric>), g, b, 0,
-                         site.stream, d_args, control);
-      break;
-    default:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentKernel<S, JAC, kCovGeneral>), g, b, 0,
-                         site.stream, d_args, control);
-      break;
-  }
-  return hipGetLastError();
-}
-}  // namespace
-
 template <typename S>
 hipError_t launchP2PLiteralResident(const P2PSweepArgs<S> *d_args, const LmControl *control,
                                     int jac_mode, int cov_mode, int grid, const LaunchSite &site) {
-  switch (jac_mode) {
-    case kJacAnalytic:
-      return launchLiteralResidentCov<S, kJacAnalytic>(d_args, control, cov_mode, grid, site);
-    case kJacAnalyticTst:
-      return launchLiteralResidentCov<S, kJacAnalyticTst>(d_args, control, cov_mode, grid, site);
-    case kJacNumeric:
-      return launchForwardDiffResident<S>(d_args, control, cov_mode, grid, site);
-    case kJacAnalyticLeft:
-      return launchLiteralResidentCov<S, kJacAnalyticLeft>(d_args, control, cov_mode, grid, site);
-    case kJacAnalyticRight:
-      return launchLiteralResidentCov<S, kJacAnalyticRight>(d_args, control, cov_mode, grid, site);
-    default:
-      return hipErrorInvalidValue;
-  }
+  if (jac_mode == kJacNumeric)
+    return launchForwardDiffResident<S>(d_args, control, cov_mode, grid, site);
+  return withP2PAnalyticJac(jac_mode, [&](auto jac) {
+    return withCov(cov_mode, [&](auto cov) {
+      return launchResident(p2pLinearizeLiteralResidentKernel<S, jac(), cov()>, grid, site.stream,
+                            d_args, control);
+    });
+  });
 }
 template hipError_t launchP2PLiteralResident<float>(const P2PSweepArgs<float> *, const LmControl *,
                                                     int, int, int, const LaunchSite &);
@@ -2149,46 +2043,16 @@ template hipError_t launchP2PLiteralResident<double>(const P2PSweepArgs<double> 
                                                      const LmControl *, int, int, int,
                                                      const LaunchSite &);
 
-namespace {
-template <typename S, int JAC>
-hipError_t launchLiteralResidentSetCov(const ResidentSweepSet &set, const LmControl *control,
-                                       int cov_mode, const LaunchSite &site) {
-  const dim3 g(set.first_block[set.num_costs]), b(kBlockThreads);
-  switch (cov_mode) {
-    case kCovIdentity:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentSetKernel<S, JAC, kCovIdentity>), g, b, 0,
-                         site.stream, set, control);
-      break;
-    case kCovSymmetric:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentSetKernel<S, JAC, kCovSymmetric>), g, b, 0,
-                         site.stream, set, control);
-      break;
-    default:
-      hipLaunchKernelGGL((p2pLinearizeLiteralResidentSetKernel<S, JAC, kCovGeneral>), g, b, 0,
-                         site.stream, set, control);
-      break;
-  }
-  return hipGetLastError();
-}
-}  // namespace
-
 template <typename S>
 hipError_t launchP2PLiteralResidentSet(const ResidentSweepSet &set, const LmControl *control,
                                        int jac_mode, int cov_mode, const LaunchSite &site) {
-  switch (jac_mode) {
-    case kJacAnalytic:
-      return launchLiteralResidentSetCov<S, kJacAnalytic>(set, control, cov_mode, site);
-    case kJacAnalyticTst:
-      return launchLiteralResidentSetCov<S, kJacAnalyticTst>(set, control, cov_mode, site);
-    case kJacNumeric:
-      return launchForwardDiffResidentSet<S>(set, control, cov_mode, site);
-    case kJacAnalyticLeft:
-      return launchLiteralResidentSetCov<S, kJacAnalyticLeft>(set, control, cov_mode, site);
-    case kJacAnalyticRight:
-      return launchLiteralResidentSetCov<S, kJacAnalyticRight>(set, control, cov_mode, site);
-    default:
-      return hipErrorInvalidValue;
-  }
+  if (jac_mode == kJacNumeric) return launchForwardDiffResidentSet<S>(set, control, cov_mode, site);
+  return withP2PAnalyticJac(jac_mode, [&](auto jac) {
+    return withCov(cov_mode, [&](auto cov) {
+      return launchResident(p2pLinearizeLiteralResidentSetKernel<S, jac(), cov()>,
+                            set.first_block[set.num_costs], site.stream, set, control);
+    });
+  });
 }
 template hipError_t launchP2PLiteralResidentSet<float>(const ResidentSweepSet &, const LmControl *,
                                                        int, int, const LaunchSite &);
@@ -2197,111 +2061,51 @@ template hipError_t launchP2PLiteralResidentSet<double>(const ResidentSweepSet &
 
 hipError_t launchReprojResident(const ReprojSweepArgs *d_args, const LmControl *control,
                                 int cov_mode, int grid, const LaunchSite &site) {
-  const dim3 g(grid), b(kBlockThreads);
-  switch (cov_mode) {
-    case kCovIdentity:
-      hipLaunchKernelGGL((reprojResidentKernel<kCovIdentity>), g, b, 0, site.stream, d_args, control);
-      break;
-    case kCovSymmetric:
-      hipLaunchKernelGGL((reprojResidentKernel<kCovSymmetric>), g, b, 0, site.stream, d_args, control);
-      break;
-    default:
-      hipLaunchKernelGGL((reprojResidentKernel<kCovGeneral>), g, b, 0, site.stream, d_args, control);
-      break;
-  }
-  return hipGetLastError();
+  return withCov(cov_mode, [&](auto cov) {
+    return launchResident(reprojResidentKernel<cov()>, grid, site.stream, d_args, control);
+  });
 }
 
 hipError_t launchReprojResidentSet(const ResidentSweepSet &set, const LmControl *control,
                                    int cov_mode, const LaunchSite &site) {
-  const dim3 g(set.first_block[set.num_costs]), b(kBlockThreads);
-  switch (cov_mode) {
-    case kCovIdentity:
-      hipLaunchKernelGGL((reprojResidentSetKernel<kCovIdentity>), g, b, 0, site.stream, set, control);
-      break;
-    case kCovSymmetric:
-      hipLaunchKernelGGL((reprojResidentSetKernel<kCovSymmetric>), g, b, 0, site.stream, set, control);
-      break;
-    default:
-      hipLaunchKernelGGL((reprojResidentSetKernel<kCovGeneral>), g, b, 0, site.stream, set, control);
-      break;
-  }
-  return hipGetLastError();
+  return withCov(cov_mode, [&](auto cov) {
+    return launchResident(reprojResidentSetKernel<cov()>, set.first_block[set.num_costs], site.stream,
+                          set, control);
+  });
 }
 
 namespace {
 template <typename S, template <typename> class ModelT>
-hipError_t launchScalarResidentFor(const ScalarSweepArgs<S> *d_args, const LmControl *control,
-                                   int jac_mode, int cov_mode, int grid, hipStream_t stream) {
-  const dim3 g(grid), b(kBlockThreads);
-  const bool numeric = (jac_mode == kJacNumeric);
-#define MOPT_LAUNCH_SCALAR_RESIDENT(JAC, COV)                                                    \
-  hipLaunchKernelGGL((scalarModelResidentKernel<S, ModelT, JAC, COV>), g, b, 0, stream, d_args, \
-                     control)
-  switch (cov_mode) {
-    case kCovIdentity:
-      if (numeric) MOPT_LAUNCH_SCALAR_RESIDENT(kJacNumeric, kCovIdentity);
-      else MOPT_LAUNCH_SCALAR_RESIDENT(kJacAnalytic, kCovIdentity);
-      break;
-    case kCovSymmetric:
-      if (numeric) MOPT_LAUNCH_SCALAR_RESIDENT(kJacNumeric, kCovSymmetric);
-      else MOPT_LAUNCH_SCALAR_RESIDENT(kJacAnalytic, kCovSymmetric);
-      break;
-    default:
-      if (numeric) MOPT_LAUNCH_SCALAR_RESIDENT(kJacNumeric, kCovGeneral);
-      else MOPT_LAUNCH_SCALAR_RESIDENT(kJacAnalytic, kCovGeneral);
-      break;
-  }
-#undef MOPT_LAUNCH_SCALAR_RESIDENT
-  return hipGetLastError();
+hipError_t launchScalarResidentFor(ScalarModel<ModelT>, const ScalarSweepArgs<S> *d_args,
+                                   const LmControl *control, int jac_mode, int cov_mode, int grid,
+                                   hipStream_t stream) {
+  return withCov(cov_mode, [&](auto cov) {
+    return withModelJac(jac_mode, [&](auto jac) {
+      return launchResident(scalarModelResidentKernel<S, ModelT, jac(), cov()>, grid, stream, d_args,
+                            control);
+    });
+  });
 }
-}  // namespace
 
-namespace {
 template <typename S, template <typename> class ModelT>
-hipError_t launchScalarResidentSetFor(const ResidentSweepSet &set, const LmControl *control,
-                                      int jac_mode, int cov_mode, hipStream_t stream) {
-  const dim3 g(set.first_block[set.num_costs]), b(kBlockThreads);
-  const bool numeric = (jac_mode == kJacNumeric);
-#define MOPT_LAUNCH_SCALAR_SET(JAC, COV)                                                          \
-  hipLaunchKernelGGL((scalarModelResidentSetKernel<S, ModelT, JAC, COV>), g, b, 0, stream, set, \
-                     control)
-  switch (cov_mode) {
-    case kCovIdentity:
-      if (numeric) MOPT_LAUNCH_SCALAR_SET(kJacNumeric, kCovIdentity);
-      else MOPT_LAUNCH_SCALAR_SET(kJacAnalytic, kCovIdentity);
-      break;
-    case kCovSymmetric:
-      if (numeric) MOPT_LAUNCH_SCALAR_SET(kJacNumeric, kCovSymmetric);
-      else MOPT_LAUNCH_SCALAR_SET(kJacAnalytic, kCovSymmetric);
-      break;
-    default:
-      if (numeric) MOPT_LAUNCH_SCALAR_SET(kJacNumeric, kCovGeneral);
-      else MOPT_LAUNCH_SCALAR_SET(kJacAnalytic, kCovGeneral);
-      break;
-  }
-#undef MOPT_LAUNCH_SCALAR_SET
-  return hipGetLastError();
+hipError_t launchScalarResidentSetFor(ScalarModel<ModelT>, const ResidentSweepSet &set,
+                                      const LmControl *control, int jac_mode, int cov_mode,
+                                      hipStream_t stream) {
+  return withCov(cov_mode, [&](auto cov) {
+    return withModelJac(jac_mode, [&](auto jac) {
+      return launchResident(scalarModelResidentSetKernel<S, ModelT, jac(), cov()>,
+                            set.first_block[set.num_costs], stream, set, control);
+    });
+  });
 }
 }  // namespace
 
 template <typename S>
 hipError_t launchScalarModelResidentSet(const ResidentSweepSet &set, const LmControl *control,
                                         int model, int jac_mode, int cov_mode, hipStream_t stream) {
-  switch (model) {
-    case kScalarExpCurve:
-      return launchScalarResidentSetFor<S, ExpCurve>(set, control, jac_mode, cov_mode, stream);
-    case kScalarRational:
-      return launchScalarResidentSetFor<S, Rational>(set, control, jac_mode, cov_mode, stream);
-    case kScalarPowell:
-      return launchScalarResidentSetFor<S, Powell>(set, control, jac_mode, cov_mode, stream);
-    case kScalarExpCurveMarked:
-      return launchScalarResidentSetFor<S, ExpCurveMarked>(set, control, jac_mode, cov_mode, stream);
-    case kScalarRationalMarked:
-      return launchScalarResidentSetFor<S, RationalMarked>(set, control, jac_mode, cov_mode, stream);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return withScalarModel(model, [&](auto kind) {
+    return launchScalarResidentSetFor<S>(kind, set, control, jac_mode, cov_mode, stream);
+  });
 }
 template hipError_t launchScalarModelResidentSet<float>(const ResidentSweepSet &, const LmControl *,
                                                         int, int, int, hipStream_t);
@@ -2312,20 +2116,9 @@ template <typename S>
 hipError_t launchScalarModelResident(const ScalarSweepArgs<S> *d_args, const LmControl *control,
                                      int model, int jac_mode, int cov_mode, int grid,
                                      hipStream_t stream) {
-  switch (model) {
-    case kScalarExpCurve:
-      return launchScalarResidentFor<S, ExpCurve>(d_args, control, jac_mode, cov_mode, grid, stream);
-    case kScalarRational:
-      return launchScalarResidentFor<S, Rational>(d_args, control, jac_mode, cov_mode, grid, stream);
-    case kScalarPowell:
-      return launchScalarResidentFor<S, Powell>(d_args, control, jac_mode, cov_mode, grid, stream);
-    case kScalarExpCurveMarked:
-      return launchScalarResidentFor<S, ExpCurveMarked>(d_args, control, jac_mode, cov_mode, grid, stream);
-    case kScalarRationalMarked:
-      return launchScalarResidentFor<S, RationalMarked>(d_args, control, jac_mode, cov_mode, grid, stream);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return withScalarModel(model, [&](auto kind) {
+    return launchScalarResidentFor<S>(kind, d_args, control, jac_mode, cov_mode, grid, stream);
+  });
 }
 template hipError_t launchScalarModelResident<float>(const ScalarSweepArgs<float> *,
                                                      const LmControl *, int, int, int, int,
@@ -2334,24 +2127,31 @@ template hipError_t launchScalarModelResident<double>(const ScalarSweepArgs<doub
                                                       const LmControl *, int, int, int, int,
                                                       hipStream_t);
 
+namespace {
+// A resident finalize kernel (one workgroup; its last three parameters are the sum over the ranks,
+// the problem and this cost's slot in it): `pick(step)` names the kernel for a step scalar — 0 where no
+// LM step is taken in this launch (`step` NULL), else LevenbergMarquadtDynamic<double | float> by
+// `scalar_bytes`.
+template <typename Pick, typename... Args>
+hipError_t launchResidentFinalize(Pick pick, hipStream_t stream, const PeerCombine *peers,
+                                  const LmProblem *step, int own_index, int scalar_bytes,
+                                  const Args &...args) {
+  const PeerCombine pc = peers ? *peers : PeerCombine();
+  return withLmStepScalar(step != nullptr, scalar_bytes, [&](auto step_scalar) {
+    hipLaunchKernelGGL(pick(step_scalar), dim3(1), dim3(kStepThreads), 0, stream, args..., pc,
+                       step ? *step : LmProblem(), step ? own_index : 0);
+    return hipGetLastError();
+  });
+}
+}  // namespace
+
 hipError_t launchFinalizeDenseResident(const double *partials, int grid, int nacc, int n,
                                        double *result, LmControl *control, hipStream_t stream,
                                        const PeerCombine *peers, const LmProblem *step,
                                        int own_index, int scalar_bytes) {
-  if (n < 1 || n > kMaxWideParams || (nacc != n * (n + 1) / 2 + n + 1 && nacc != n * n + n + 1))
-    return hipErrorInvalidValue;
-  const PeerCombine pc = peers ? *peers : PeerCombine();
-  const dim3 g(1), b(kStepThreads);
-  if (!step)
-    hipLaunchKernelGGL(finalizeDenseResidentKernel<0>, g, b, 0, stream, partials, grid, nacc, n,
-                       result, control, pc, LmProblem(), 0);
-  else if (scalar_bytes == 8)
-    hipLaunchKernelGGL(finalizeDenseResidentKernel<8>, g, b, 0, stream, partials, grid, nacc, n,
-                       result, control, pc, *step, own_index);
-  else
-    hipLaunchKernelGGL(finalizeDenseResidentKernel<4>, g, b, 0, stream, partials, grid, nacc, n,
-                       result, control, pc, *step, own_index);
-  return hipGetLastError();
+  if (n < 1 || n > kMaxWideParams || !isDenseRow(nacc, n)) return hipErrorInvalidValue;
+  return launchResidentFinalize([](auto s) { return finalizeDenseResidentKernel<s()>; }, stream, peers,
+                                step, own_index, scalar_bytes, partials, grid, nacc, n, result, control);
 }
 
 hipError_t launchFinalizeEitherResident(const double *partials, int grid_moments, int grid_literal,
@@ -2360,18 +2160,9 @@ hipError_t launchFinalizeEitherResident(const double *partials, int grid_moments
                                         const PeerCombine *peers, const LmProblem *step,
                                         int own_index, int scalar_bytes) {
   if (nacc != kAccSym && nacc != kAccFull) return hipErrorInvalidValue;
-  const PeerCombine pc = peers ? *peers : PeerCombine();
-  const dim3 g(1), b(kStepThreads);
-  if (!step)
-    hipLaunchKernelGGL(finalizeEitherResidentKernel<0>, g, b, 0, stream, partials, grid_moments,
-                       grid_literal, nacc, d_basis, result, control, pc, LmProblem(), 0);
-  else if (scalar_bytes == 8)
-    hipLaunchKernelGGL(finalizeEitherResidentKernel<8>, g, b, 0, stream, partials, grid_moments,
-                       grid_literal, nacc, d_basis, result, control, pc, *step, own_index);
-  else
-    hipLaunchKernelGGL(finalizeEitherResidentKernel<4>, g, b, 0, stream, partials, grid_moments,
-                       grid_literal, nacc, d_basis, result, control, pc, *step, own_index);
-  return hipGetLastError();
+  return launchResidentFinalize([](auto s) { return finalizeEitherResidentKernel<s()>; }, stream, peers,
+                                step, own_index, scalar_bytes, partials, grid_moments, grid_literal,
+                                nacc, d_basis, result, control);
 }
 
 hipError_t launchFinalizeMomentsResident(const double *partials, int grid,
@@ -2379,18 +2170,8 @@ hipError_t launchFinalizeMomentsResident(const double *partials, int grid,
                                          LmControl *control, hipStream_t stream,
                                          const PeerCombine *peers, const LmProblem *step,
                                          int own_index, int scalar_bytes) {
-  const PeerCombine pc = peers ? *peers : PeerCombine();
-  const dim3 g(1), b(kStepThreads);
-  if (!step)
-    hipLaunchKernelGGL(finalizeMomentsResidentKernel<0>, g, b, 0, stream, partials, grid, d_basis,
-                       result, control, pc, LmProblem(), 0);
-  else if (scalar_bytes == 8)
-    hipLaunchKernelGGL(finalizeMomentsResidentKernel<8>, g, b, 0, stream, partials, grid, d_basis,
-                       result, control, pc, *step, own_index);
-  else
-    hipLaunchKernelGGL(finalizeMomentsResidentKernel<4>, g, b, 0, stream, partials, grid, d_basis,
-                       result, control, pc, *step, own_index);
-  return hipGetLastError();
+  return launchResidentFinalize([](auto s) { return finalizeMomentsResidentKernel<s()>; }, stream, peers,
+                                step, own_index, scalar_bytes, partials, grid, d_basis, result, control);
 }
 
 }  // namespace mopt

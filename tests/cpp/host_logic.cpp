@@ -10,7 +10,9 @@
 #include <random>
 #include <sstream>
 #include <stdexcept>
+#include <type_traits>
 
+#include "dispatch.hpp"
 #include "moptimizer_amd/cost_function_hip.hpp"
 #include "moptimizer_caller/levenberg_marquadt.hpp"
 #include "moptimizer_amd/so3.hpp"
@@ -345,8 +347,91 @@ static void lossThresholdRecovery() {
   lossThresholdRecoveryFor<float>("float", 1e-6, 2e-3);
 }
 
+// csrc/dispatch.hpp: a run-time value reaches the lambda as the compile-time tag of that same value, an
+// unlisted one takes what the call states (the default's tag, or the failure value without running the
+// lambda), and the lambda's return value comes back.
+template <typename Tag>
+static int tagValue(Tag) { return Tag::value; }
+template <typename T>
+static int typeBytes(mopt::dispatch::Type<T>) {
+  static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "a scalar type");
+  return std::is_same<T, double>::value ? 8 : 4;
+}
+
+static void dispatchPrimitives() {
+  namespace dispatch = mopt::dispatch;
+  for (int v : {-1, 0, 3, 7}) {
+    int calls = 0;
+    const int got = dispatch::intOrFail<-1, 0, 3, 7>(v, -100, [&](auto tag) {
+      static_assert(decltype(tag)::value == tag(), "tag() is the value, a constant expression");
+      constexpr int as_template_argument = tag();
+      ++calls;
+      return 10 * as_template_argument + 1;
+    });
+    expectTrue("intOrFail: a listed value reaches its own tag, once", got == 10 * v + 1 && calls == 1);
+    expectTrue("intOrDefault: a listed value reaches its own tag",
+               (dispatch::intOrDefault<3, -1, 0, 7>(v, [](auto tag) { return tagValue(tag); })) == v);
+  }
+  for (int v : {-2, 1, 2, 8, 1 << 30}) {
+    int calls = 0;
+    const int got = dispatch::intOrFail<-1, 0, 3, 7>(v, -100, [&](auto tag) {
+      ++calls;
+      return tagValue(tag);
+    });
+    expectTrue("intOrFail: an unlisted value returns the failure value, the lambda not run",
+               got == -100 && calls == 0);
+    expectTrue("intOrDefault: an unlisted value takes the default's tag",
+               (dispatch::intOrDefault<3, -1, 0, 7>(v, [](auto tag) { return tagValue(tag); })) == 3);
+  }
+  expectTrue("intOrDefault: the default itself need not be listed",
+             (dispatch::intOrDefault<2, 0, 1>(2, [](auto tag) { return tagValue(tag); })) == 2);
+  expectTrue("intOrFail: one listed value",
+             (dispatch::intOrFail<5>(5, -1, [](auto tag) { return tagValue(tag); })) == 5 &&
+                 (dispatch::intOrFail<5>(4, -1, [](auto tag) { return tagValue(tag); })) == -1);
+  // the return type is the lambda's, not int
+  const std::string text = dispatch::intOrDefault<0, 1>(1, [](auto tag) { return std::to_string(tag()) + "!"; });
+  expectTrue("the lambda's return value comes back (a std::string)", text == "1!");
+
+  expectTrue("byBool(true) -> std::true_type",
+             dispatch::byBool(true, [](auto flag) { return std::is_same<decltype(flag), std::true_type>::value; }));
+  expectTrue("byBool(false) -> std::false_type",
+             dispatch::byBool(false, [](auto flag) { return std::is_same<decltype(flag), std::false_type>::value; }));
+  expectTrue("byBool: flag() is a constant expression", dispatch::byBool(true, [](auto flag) {
+    constexpr bool as_template_argument = flag();
+    return std::integral_constant<bool, as_template_argument>::value;
+  }));
+
+  expectTrue("widthOrFail(8) -> double", dispatch::widthOrFail(8, -1, [](auto s) { return typeBytes(s); }) == 8);
+  expectTrue("widthOrFail(4) -> float", dispatch::widthOrFail(4, -1, [](auto s) { return typeBytes(s); }) == 4);
+  for (int bytes : {0, 2, 16, -8}) {
+    int calls = 0;
+    const int got = dispatch::widthOrFail(bytes, -1, [&](auto s) {
+      ++calls;
+      return typeBytes(s);
+    });
+    expectTrue("widthOrFail: another width returns the failure value, the lambda not run", got == -1 && calls == 0);
+    expectTrue("widthOrDefault<float>: another width is float",
+               dispatch::widthOrDefault<float>(bytes, [](auto s) { return typeBytes(s); }) == 4);
+    expectTrue("widthOrDefault<double>: another width is double",
+               dispatch::widthOrDefault<double>(bytes, [](auto s) { return typeBytes(s); }) == 8);
+  }
+  expectTrue("widthOrDefault<float>(8) -> double",
+             dispatch::widthOrDefault<float>(8, [](auto s) { return typeBytes(s); }) == 8);
+  expectTrue("widthOrDefault<double>(4) -> float",
+             dispatch::widthOrDefault<double>(4, [](auto s) { return typeBytes(s); }) == 4);
+  // nested, as the launchers use it: every combination reaches its own pair of tags
+  for (int a : {0, 1, 2})
+    for (bool b : {false, true}) {
+      const int got = dispatch::intOrDefault<2, 0, 1>(a, [&](auto x) {
+        return dispatch::byBool(b, [&](auto y) { return std::integral_constant<int, 2 * x() + (y() ? 1 : 0)>::value; });
+      });
+      expectTrue("nested dispatch reaches the pair's own instantiation", got == 2 * a + (b ? 1 : 0));
+    }
+}
+
 int main() {
   optimizerStatuses();
+  dispatchPrimitives();
   ldlt();
   denseAndSo3();
   lossThresholdRecovery();

@@ -721,6 +721,57 @@ def test_p2p_float32_all_modes_against_float_oracle(hip_lib, oracle, jac_mode):
     check(cost.linearize(x, jac_mode), tuple(np.asarray(v, dtype=np.float64) for v in want), tol=tol)
 
 
+@pytest.mark.parametrize("jac_mode", [0, 1, 2, 3, 4])
+def test_p2p_float32_general_covariance_against_float_oracle(hip_lib, oracle, jac_mode):
+    """The fp32 per-point sweeps under a covariance that is not symmetric (rows of the whole H), the
+    one covariance form the test above leaves out: every Jacobian mode, the same oracle run in float
+    and the same bounds; 1025 correspondences are one past a tile."""
+    src, tgt = ds.synthetic_pair(1025, seed=21, noise=0.02, dtype=np.float32)
+    x = np.array([0.5, -0.3, 0.2, 0.1, -0.2, 0.3], dtype=np.float32)
+    cov = np.array([[2.0, 0.7, -0.1], [0.3, 0.5, 0.9], [-0.4, 0.2, 1.5]], dtype=np.float32)
+    cost = hip_lib.Point2PointCost(src, tgt, dtype=np.float32)
+    cost.set_loss(1, 100.0)
+    cost.set_covariance(cov)
+    cc = ob.NUMERIC_DYN if jac_mode == 2 else ob.ANALYTIC_DYN
+    layout = {1: ob.LAYOUT_TST, 3: ob.LAYOUT_LEFT, 4: ob.LAYOUT_RIGHT}.get(jac_mode, ob.LAYOUT_ROW_MAJOR)
+    want = oracle.p2p_linearize(src, tgt, x, cost_class=cc, layout=layout, loss_kind=1,
+                                loss_param=100.0, cov=cov, dtype=np.float32)
+    tol = 2e-3 if jac_mode == 2 else 2e-5
+    for variant in (hip_lib.KERNEL_AUTO, hip_lib.KERNEL_LITERAL):
+        cost.set_kernel_variant(variant)
+        check(cost.linearize(x, jac_mode), tuple(np.asarray(v, dtype=np.float64) for v in want), tol=tol)
+
+
+@pytest.mark.parametrize("n", [3, 1025])
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_scalar_models_under_a_covariance_in_both_widths(hip_lib, oracle, n, dtype):
+    """What test_small_parametric_models_match_oracle leaves out of the scalar launcher's selection: the
+    rational model under a covariance (m = 1: a weight) with both Jacobians in both widths, and the
+    Powell model under a covariance that is not symmetric (fp64: the oracle has neither a float Powell
+    nor a float exponential curve).  Bounds as there."""
+    rng = np.random.default_rng(5)
+    fp64 = dtype == np.float64
+    tr = np.abs(rng.normal(1.0, 1.0, n)) + 0.05
+    yr = 0.36 * tr / (0.56 + tr) + rng.normal(0, 0.01, n)
+    x = np.array([0.9, 0.2], dtype=dtype)
+    cov = np.array([[0.5]])
+    c = hip_lib.ScalarModelCost(hip_lib.capi.MODEL_RATIONAL, tr, yr, dtype=dtype)
+    c.set_covariance(cov)
+    for numeric in (True, False):
+        want = oracle.scalar_linearize(2, tr, yr, x, numeric=numeric, cov=cov, dtype=dtype)
+        want = tuple(np.asarray(v, dtype=np.float64) for v in want)
+        check(c.linearize(x, 2 if numeric else 0), want,
+              tol=5e-3 if not fp64 else (fd_tolerance_libm(x) if numeric else REL))
+    if fp64 and n == 3:  # (the Powell model has no data: once)
+        c = hip_lib.ScalarModelCost(hip_lib.capi.MODEL_POWELL)
+        xp = np.array([3.0, -1.0, 0.0, 4.0])
+        general = np.array([[1.0, 0.2, 0.0, 0.1], [0.0, 0.5, 0.3, 0.0], [0.1, 0.0, 2.0, 0.4], [0.0, -0.2, 0.0, 1.5]])
+        c.set_covariance(general)
+        for numeric in (True, False):
+            want = oracle.scalar_linearize(3, None, None, xp, numeric=numeric, cov=general)
+            check(c.linearize(xp, 2 if numeric else 0), want, tol=fd_tolerance_libm(xp) if numeric else REL)
+
+
 def test_small_parametric_models_match_oracle(hip_lib, oracle):
     """Exp-curve, rational and Powell device models (n = 2, 2, 4) against the restated CPU cost
     classes: forward-difference and analytic Jacobians, loss and covariance, fp64 and fp32."""
