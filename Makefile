@@ -17,7 +17,7 @@ LIB         = $(LIBDIR)/libmoptimizer_hip.so
 
 PUBLIC_HEADERS = include/moptimizer_hip.h include/moptimizer_amd/so3.hpp $(CSRC)/sweep.hpp $(CSRC)/fd_device.hpp \
                  $(CSRC)/sweep_device.hpp $(CSRC)/jit_model.hpp $(CSRC)/cost_state.hpp $(CSRC)/lm_device.hpp $(CSRC)/aql.hpp \
-                 $(CSRC)/dispatch.hpp
+                 $(CSRC)/dispatch.hpp $(CSRC)/sweep_choice.hpp
 
 all: $(LIB)
 
@@ -41,7 +41,8 @@ $(OBJDIR)/icp_grid.o: $(CSRC)/icp_grid.hip $(PUBLIC_HEADERS) | $(OBJDIR)
 $(OBJDIR)/lm_kernels.o: $(CSRC)/lm_kernels.hip $(PUBLIC_HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -c $< -o $@
 
-OBJS = $(OBJDIR)/sweep_kernels.o $(OBJDIR)/fd_kernels.o $(OBJDIR)/icp_grid.o $(OBJDIR)/c_abi.o $(OBJDIR)/icp.o \
+OBJS = $(OBJDIR)/sweep_kernels.o $(OBJDIR)/fd_kernels.o $(OBJDIR)/icp_grid.o $(OBJDIR)/c_abi.o $(OBJDIR)/cost.o \
+       $(OBJDIR)/sweep_launch.o $(OBJDIR)/blocking.o $(OBJDIR)/resident.o $(OBJDIR)/icp.o \
        $(OBJDIR)/group.o $(OBJDIR)/aql.o $(OBJDIR)/jit_model.o $(OBJDIR)/device_pool.o $(OBJDIR)/combine.o $(OBJDIR)/lm.o $(OBJDIR)/lm_kernels.o
 
 $(LIB): $(OBJS) | $(LIBDIR)

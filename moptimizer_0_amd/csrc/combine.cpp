@@ -4,7 +4,7 @@
 //   MOPT_COMBINE_PEER  one slot block per rank in uncached device memory, exported / opened as
 //                      hipIpcMemHandle (xGMI stores between the GPUs of a node).
 // The pushes and waits themselves are in the finalize kernels (sweep_kernels.hip: publishToHost,
-// peerCombine) and in blockingSweep (c_abi.cpp).
+// peerCombine) and in blockingSweep (blocking.cpp).
 #include "cost_state.hpp"
 
 #include <fcntl.h>

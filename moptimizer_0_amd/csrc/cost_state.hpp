@@ -1,6 +1,8 @@
-// State behind the opaque handles of include/moptimizer_hip.h and the helpers the translation
-// units of the C ABI share (c_abi.cpp: costs and sweeps; icp.cpp: correspondence search;
-// group.cpp: single-process device group).  Internal to libmoptimizer_hip.so.
+// State behind the opaque handles of include/moptimizer_hip.h, and what the host translation units of
+// libmoptimizer_hip.so share: the TRY macros, the scalar-type dispatch, and the declarations of the
+// functions one unit defines for the others, grouped by that unit (cost.cpp: lifetime; sweep_launch.cpp:
+// one sweep on a stream; blocking.cpp: publish and wait; resident.cpp: the device-resident LM's sweeps;
+// c_abi.cpp, device_pool.cpp, combine.cpp, icp.cpp).  Internal to the library.
 #pragma once
 
 #include "moptimizer_hip.h"
@@ -141,19 +143,17 @@ struct mopt_cost {
   // set around the launches of one sweep: the finalize kernel then also adds over the ranks
   const mopt::PeerCombine *launch_peers = nullptr;
   // Direct dispatch of the blocking sweeps (aql.hpp).  `aql_queue`: this cost's queue of the device's
-  // pool (drawn on first use); `aql_now`: set around the launches of a sweep that may go there;
-  // `aql_touched`: something was dispatched there since the queue was last drained (memory of this
-  // cost must not be recycled before a drain); `hip_pending`: something was queued on `stream` that
-  // a direct sweep would have to wait for (a path switch synchronises once).
+  // pool (drawn on first use).  What the six flags below mean and who sets each stands with their
+  // transitions, at the top of blocking.cpp.
   mopt_detail::AqlQueue *aql_queue = nullptr;
   bool aql_tried = false;
   bool aql_retained = false;  // counted by aqlRetain: aqlRelease when the cost goes
   mopt_detail::AqlSite aql_now;
   bool aql_touched = false;
   bool hip_pending = false;
-  bool waiting_direct = false;  // the sweep being waited for went through the direct path
-  bool sweep_went_direct = false;  // set by the launch itself (SweepTimer::aql) when it did
-  bool aql_timed = false;       // ... and its dispatch is being timed (profiling)
+  bool waiting_direct = false;
+  bool sweep_went_direct = false;
+  bool aql_timed = false;
 
   double cov[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};  // row-major, stride 3 (m <= 3), as double
   double cov_m[mopt::kMaxWideOutputs * mopt::kMaxWideOutputs] = {1};  // row-major m x m compact (generic models)
@@ -241,67 +241,135 @@ namespace mopt_detail {
 using mopt::kNumParams;
 using mopt::kResultDoubles;
 
-// Non-blocking streams are recycled per device: creating one costs the runtime ~1.5 ms and
-// destroying it ~1.2 ms, which would dominate the construction of a small cost.  A released
-// stream has been synchronised by its last owner.  (Streams still pooled at process exit are
-// left to the runtime's own teardown.)
-hipError_t acquireStream(int device, hipStream_t *out);
-void releaseStream(int device, hipStream_t stream);
+// results of one sweep in d_result / h_result: H (n x n) | b (n) | sum_sq
+inline int resultCount(const mopt_cost *c) { return c->n_params * c->n_params + c->n_params + 1; }
+inline int costOffset(const mopt_cost *c) { return c->n_params * c->n_params + c->n_params; }
 
-// Device memory of the current device through the size-class cache of device_pool.cpp.  Release
-// only after the work that used the block has completed.
+// ---- c_abi.cpp ---------------------------------------------------------------------------------
+// set by mopt_icp_create around the point2point cost it builds on: a cost with a correspondence search
+// never takes the direct dispatch path, so its creation does not warm a queue (aql.hpp aqlWarm)
+extern thread_local bool g_creating_for_search;
+
+// ---- device_pool.cpp ---------------------------------------------------------------------------
+// Device memory of the current device through the size-class cache.  Release only after the work
+// that used the block has completed.
 hipError_t deviceAlloc(void **out, size_t bytes);
 void deviceRelease(void *p);
 // mapped, coherent host blocks (a cost's published results), cached per device and size
 hipError_t mappedHostAlloc(void **out, size_t bytes);
 void mappedHostRelease(int device, void *p, size_t bytes);
 
-int commonCreate(mopt_cost *c, int device);  // device, stream, partial / result buffers
+// ---- combine.cpp, icp.cpp ----------------------------------------------------------------------
+// unmaps / closes whatever combine transport was attached
+void releaseCombine(mopt_cost *c);
+// the pose-independent part of a correspondence search over this cost's grid
+template <typename S>
+void fillIcpArgs(const mopt_cost *c, mopt::IcpMatchArgs<S> &a);
+
+// ---- cost.cpp: lifetime ------------------------------------------------------------------------
+// Non-blocking streams are recycled per device: creating one costs the runtime ~1.5 ms and
+// destroying it ~1.2 ms, which would dominate the construction of a small cost.  A released
+// stream has been synchronised by its last owner.  (Streams still pooled at process exit are
+// left to the runtime's own teardown.)
+hipError_t acquireStream(int device, hipStream_t *out);
+void releaseStream(int device, hipStream_t stream);
+// device, stream, partial / result buffers
+int commonCreate(mopt_cost *c, int device);
 // wait for everything enqueued for this cost, on its own stream and on callers' streams
 hipError_t quiesceCost(mopt_cost *c);
-void releaseCombine(mopt_cost *c);  // combine.cpp: unmaps / closes whatever was attached
-// c_abi.cpp, for the device-resident LM (lm.cpp): upload the static part of this cost's sweep
-// constants if it changed and describe the cost to the step kernel; enqueue one resident sweep +
-// finalize on `s` (peer-combine sequence numbers = base_sequence + trials counted on the device)
-// c_abi.cpp: the next (host_result, flag, sequence) of this cost's mapped host block, and the wait
-mopt::HostPublish nextHostPublish(mopt_cost *c, int offset);
-int waitHostPublished(mopt_cost *c, unsigned long long sequence);
-// `partials_override`: write this cost's partial rows there instead of into its own buffer (the
-// rows of several costs behind one another, reduced by one finalize kernel)
+// quiesce, then give back everything the cost holds and the cost itself (NULL: nothing)
+void destroyCost(mopt_cost *c);
+// H | b | sum_sq as doubles -> the caller's arrays in the cost's scalar type
+void storeResult(const mopt_cost *c, const double *res, void *hessian, void *b, void *sum_sq);
+
+// ---- sweep_launch.cpp: one sweep + finalize on a stream ----------------------------------------
+// Templates are defined there and instantiated for float and double.
+// enqueue one linearization sweep + its finalize on `s`; results to d_result (+ optional hand-over to
+// mapped host memory)
+int linearizeAsyncImpl(mopt_cost *c, int jac_mode, const void *x, double *d_result, hipStream_t s,
+                       const mopt::HostPublish &pub = mopt::HostPublish());
+// the same for the cost sweep; the sum to d_sum
+int costAsyncImpl(mopt_cost *c, const void *x, double *d_sum, hipStream_t s,
+                  const mopt::HostPublish &pub = mopt::HostPublish());
+// read the timing of every pending event pair into the cost's sweep statistics
+int resolvePendingEvents(mopt_cost *c);
+// forward-difference points of the reference: h_j = sqrt(eps) |x_j| (or sqrt(eps)), x_plus_j = x + h_j e_j
+template <typename S>
+void forwardSteps(const S *x, S h[kNumParams], S x_plus[kNumParams][kNumParams]);
+// a point2point sweep's arguments at x (`with_steps`: the six forward-difference poses as well)
+template <typename S>
+void fillP2PArgs(const mopt_cost *c, const S *x, bool with_steps, mopt::P2PSweepArgs<S> &a);
+// the affine Jacobian basis J(p) = J0 + sum_k p_k J_k of `jac_mode` at the pose in `a`, and the covariance
+template <typename S>
+void fillBasis(const mopt_cost *c, int jac_mode, const mopt::P2PSweepArgs<S> &a, mopt::AffineBasis &B);
+// a reprojection sweep's arguments: (K T(x)) C, and with `with_steps` the six stepped products
+void fillReprojArgs(const mopt_cost *c, const double *x, bool with_steps, mopt::ReprojSweepArgs &a);
+// the arguments of a built-in scalar model's sweep: x, its forward steps, data, loss, covariance
+template <typename S>
+void fillScalarArgs(const mopt_cost *c, const S *x, mopt::ScalarSweepArgs<S> &a);
+// the same in the layout a run-time compiled sweep takes ...
+template <typename S>
+void fillJitArgs(const mopt_cost *c, const S *x, mopt::JitArgs<S> &args);
+// ... and a wide one (n > 8 or m > 4)
+template <typename S>
+void fillJitWideArgs(const mopt_cost *c, const S *x, mopt::JitWideArgs<S> &args);
+// The Jacobian modes of the generic models (built-in scalar and run-time compiled; blocking calls and
+// the device-resident loop): forward differences always, the model's own where it has one.
+int checkModelJacobian(const mopt_cost *c, int jac_mode);
+// workgroups per CU of a tiled sweep: `fallback` unless MOPT_BLOCKS_PER_CU overrides it
+int blocksPerCu(int fallback);
+// workgroups (= partial rows) of a tiled sweep of this cost (sweep_choice.hpp gridFor)
+int gridFor(const mopt_cost *c, int blocks_per_cu);
+// ... of a built-in scalar model's sweep: a workgroup per 256 packs of 16 bytes, at most four per CU
+int scalarGrid(const mopt_cost *c);
+// ... of a run-time compiled model's sweep
+int jitGrid(const mopt_cost *c);
+// values per partial row of a run-time compiled model's sweep (a wide one has the general form only)
+int jitDenseRow(const mopt_cost *c);
+
+// ---- blocking.cpp: publish and wait ------------------------------------------------------------
+// the next (host_result + offset, flag, sequence) of this cost's mapped host block
+mopt::HostPublish nextPublish(mopt_cost *c, int offset);
+// poll the flag word of that block until `sequence` arrives; a faulted sweep or 60 s is an error
+int waitPublished(mopt_cost *c, unsigned long long sequence);
+// the finalize kernel's view of the ranks' peer blocks for the collective sweep numbered `sequence`
+mopt::PeerCombine peerCombineAt(const ShardCombine &sc, int offset, unsigned long long sequence);
+// launch one sweep + finalize of a cost, published into its own mapped host memory, without waiting
+// (group.cpp: one thread launches, another waits; linked costs: queued ahead) ...
+int launchPublishedSweep(mopt_cost *c, bool cost_only, int jac_mode, const void *x,
+                         unsigned long long *sequence_out);
+// ... and the wait for that publication
+int waitPublishedSweep(mopt_cost *c, unsigned long long sequence);
+
+// ---- resident.cpp: sweeps of the device-resident LM (lm.cpp) -----------------------------------
+// Upload the static part of this cost's sweep constants if it changed and describe the cost to the
+// step kernel.  `partials_override`: write this cost's partial rows there instead of into its own
+// buffer (the rows of several costs behind one another, reduced by one finalize kernel).
 int residentPrepare(mopt_cost *c, int jac_mode, hipStream_t s, mopt::LmCostDesc *desc,
                     double *partials_override = nullptr);
-int residentGrid(const mopt_cost *c, int jac_mode);      // workgroups (= partial rows) of a resident sweep
-int residentDenseRow(const mopt_cost *c, int jac_mode);  // values per partial row; 0: rows of moments
+// workgroups (= partial rows) of a resident sweep
+int residentGrid(const mopt_cost *c, int jac_mode);
+// values per partial row; 0: rows of moments
+int residentDenseRow(const mopt_cost *c, int jac_mode);
 // point2point forward differences under AUTO / MOMENTS: moments or literal, chosen per evaluated point
 bool residentPerIterate(const mopt_cost *c, int jac_mode);
-// set by mopt_icp_create around the point2point cost it builds on: a cost with a correspondence search
-// never takes the direct dispatch path, so its creation does not warm a queue (aql.hpp aqlWarm)
-extern thread_local bool g_creating_for_search;
-// one finalize (+ LM step) over `rows` rows of `row_length` values in last->d_partials
-int residentFinalizeMerged(mopt_cost *last, int rows, int row_length, mopt::LmControl *control,
-                           hipStream_t s, const mopt::LmProblem *step, int own_index);
-// `step` non-NULL: this is the last cost of the problem, its finalize kernel also runs the LM step
-// the resident sweeps of all costs in one launch, where a kernel for that exists (reprojection
-// costs with one covariance form); first_row[k] = where cost k's partial rows start
-bool residentSetSupported(mopt_cost *const *costs, int num_costs, const int *jac_modes);
-int residentSweepSet(mopt_cost *const *costs, int num_costs, const int *jac_modes,
-                     const int *first_row, mopt::LmControl *control, hipStream_t s);
+// Enqueue one resident sweep (+ finalize, unless `finalize` is false) on `s`; peer-combine sequence
+// numbers = base_sequence + trials counted on the device.  `step` non-NULL: this is the last cost of
+// the problem, its finalize kernel also runs the LM step.
 int residentSweep(mopt_cost *c, int jac_mode, mopt::LmControl *control, hipStream_t s,
                   unsigned long long base_sequence, const mopt::LmProblem *step = nullptr,
                   int own_index = 0, bool finalize = true);
+// Can the resident sweeps of these costs (whose rows already lie behind one another) go out as ONE
+// launch?  They must run the same kernel.
+bool residentSetSupported(mopt_cost *const *costs, int num_costs, const int *jac_modes);
+// the resident sweeps of all costs in that one launch; first_row[k] = where cost k's partial rows start
+int residentSweepSet(mopt_cost *const *costs, int num_costs, const int *jac_modes,
+                     const int *first_row, mopt::LmControl *control, hipStream_t s);
+// one finalize (+ LM step) over `rows` rows of `row_length` values in last->d_partials
+int residentFinalizeMerged(mopt_cost *last, int rows, int row_length, mopt::LmControl *control,
+                           hipStream_t s, const mopt::LmProblem *step, int own_index);
+// give back the resident constants, workspace and report block of this cost
 void releaseResident(mopt_cost *c);
-// icp.cpp: the pose-independent part of a correspondence search over this cost's grid
-template <typename S>
-void fillIcpArgs(const mopt_cost *c, mopt::IcpMatchArgs<S> &a);
-void destroyCost(mopt_cost *c);
-// enqueue one linearization / cost sweep + its finalize on `s`; results to d_result (+ optional
-// hand-over to mapped host memory)
-int linearizeAsyncImpl(mopt_cost *c, int jac_mode, const void *x, double *d_result, hipStream_t s,
-                       const mopt::HostPublish &pub = mopt::HostPublish());
-int costAsyncImpl(mopt_cost *c, const void *x, double *d_sum, hipStream_t s,
-                  const mopt::HostPublish &pub = mopt::HostPublish());
-// H | b | sum_sq as doubles -> the caller's arrays in the cost's scalar type
-void storeResult(const mopt_cost *c, const double *res, void *hessian, void *b, void *sum_sq);
 
 // Back to the device pool on scope exit, after whatever was queued on `stream` — the stream the
 // block was used on — has run (an early return may leave work behind; on the normal path the

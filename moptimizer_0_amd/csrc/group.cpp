@@ -20,14 +20,6 @@
 
 using namespace mopt_detail;
 
-namespace mopt_detail {
-// c_abi.cpp: launch one sweep + finalize of a shard, published into its own mapped host memory,
-// without waiting; and the wait for that publication
-int launchPublishedSweep(mopt_cost *c, bool cost_only, int jac_mode, const void *x,
-                         unsigned long long *sequence_out);
-int waitPublishedSweep(mopt_cost *c, unsigned long long sequence);
-}  // namespace mopt_detail
-
 struct mopt_group {
   std::vector<mopt_cost *> shards;
   std::vector<ncclComm_t> comms;
@@ -62,8 +54,7 @@ void runShardJob(mopt_group *g, int k) {
   if (rc == MOPT_OK) {
     if (g->use_rccl) {
       rc = g->job.cost_only
-               ? costAsyncImpl(c, g->job.x, c->d_result + (c->n_params * c->n_params + c->n_params),
-                               c->stream)
+               ? costAsyncImpl(c, g->job.x, c->d_result + costOffset(c), c->stream)
                : linearizeAsyncImpl(c, g->job.jac_mode, g->job.x, c->d_result, c->stream);
     } else {
       rc = launchPublishedSweep(c, g->job.cost_only, g->job.jac_mode, g->job.x, &g->sequence[k]);

@@ -193,9 +193,9 @@ int icpUpdate(mopt_cost *c, const S *x, int64_t *num_matched) {
     // the count comes back like a sweep result: a one-wave kernel stores it into mapped host
     // memory and releases a sequence word — no memset, no copy, no stream synchronisation
     const int slot = mopt_detail::kResultSlots - 1;  // beyond any n*n + n + 1 <= 73
-    const mopt::HostPublish pub = nextHostPublish(c, slot);
+    const mopt::HostPublish pub = nextPublish(c, slot);
     MOPT_HIP_TRY(mopt::launchPublishCounter(mt.d_matched, mt.num_waves, pub, c->stream));
-    const int rc = waitHostPublished(c, pub.sequence);
+    const int rc = waitPublished(c, pub.sequence);
     if (rc != MOPT_OK) return rc;
     *num_matched = int64_t(c->h_result[slot]);
   }

@@ -1,4 +1,5 @@
-// Run-time compiled device models (hipRTC): internal interface between c_abi.cpp and jit_model.cpp.
+// Run-time compiled device models (hipRTC): internal interface between the units that create and
+// launch such a model (cost.cpp, sweep_launch.cpp, resident.cpp) and jit_model.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -390,7 +390,7 @@ __device__ bool solveDampedPositive(const S *H, const S *b, S lambda, S *delta) 
 }
 
 // (K T) C, row-major 3x4: the matrix products of tst/camera_calibration.cpp:37 in the association
-// of the host statement (c_abi.cpp projectionFor).
+// of the host statement (sweep_launch.cpp projectionFor).
 __device__ void projectionFor(const LmCostDesc &d, const double (&T)[12], double (&M)[12]) {
 #pragma clang fp contract(off)
   double T4[16];
@@ -458,7 +458,7 @@ __device__ __forceinline__ void writeSweepConstants(const LmProblem &P, const S 
         if (tid < (1 + kNumParams) * 12) a->T[tid / 12][tid % 12] = Tj(tid / 12)[tid % 12];
         if (tid < kNumParams) a->inv_h[tid] = inv_h_of(tid);
         if (d.moments && d.jac_mode == kJacAnalyticLeft && tid < 18) {
-          // J(p) = [I | -skew(R p + t)] = J0 + sum_k p_k J_k (c_abi.cpp fillBasis)
+          // J(p) = [I | -skew(R p + t)] = J0 + sum_k p_k J_k (sweep_launch.cpp fillBasis)
           const int r = tid / 6, j = tid % 6;
           auto pattern = [&](const S (&w)[3]) -> S {  // entry (r, j) of [I | -skew(w)]
             if (j < 3) return r == j ? S(1) : S(0);
@@ -479,7 +479,7 @@ __device__ __forceinline__ void writeSweepConstants(const LmProblem &P, const S 
           }
         }
         if (d.moments && d.jac_mode == kJacAnalyticRight && tid < 18) {
-          // J(p) = [I | -R skew(p)]: J0 = [I | 0], J_k = [0 | -R skew(e_k)] (c_abi.cpp fillBasis).
+          // J(p) = [I | -R skew(p)]: J0 = [I | 0], J_k = [0 | -R skew(e_k)] (sweep_launch.cpp fillBasis).
           // skew(e_k)(m, c) = -eps(m, c, k): column c != k has its one entry in row m = 3 - c - k.
           const int r = tid / 6, j = tid % 6;
           basis->J[0][r * 6 + j] = (j < 3 && r == j) ? 1.0 : 0.0;
@@ -499,7 +499,7 @@ __device__ __forceinline__ void writeSweepConstants(const LmProblem &P, const S 
           }
         }
         if (d.moments && numeric && tid < 18) {
-          // column j of J is ((R_j - R) p + (t_j - t)) / h_j  (c_abi.cpp fillBasis)
+          // column j of J is ((R_j - R) p + (t_j - t)) / h_j  (sweep_launch.cpp fillBasis)
           const int r = tid / 6, j = tid % 6;
           basis->J[0][r * 6 + j] = double((Tj(1 + j)[r * 4 + 3] - Tj(0)[r * 4 + 3]) * inv_h_of(j));
           for (int k = 0; k < 3; ++k)
@@ -807,7 +807,7 @@ __device__ __forceinline__ bool lmStepBodyFor(const LmProblem &P, bool init, con
     st.status = status;
     st.steps += 1;
     // Which forward-difference sweep the next point takes (costs of LmProblem::fd_per_iterate): the rule
-    // of the blocking call (c_abi.cpp hasSmallForwardStep) at the very x that sweep is evaluated at.
+    // of the blocking call (sweep_choice.hpp hasSmallForwardStep) at the very x that sweep is evaluated at.
     // (Compiled out of the one-launch solve that holds the moments only: lm.cpp keeps such problems out of
     // it, and the code cost that kernel a hundred spilled scalar registers.)
     literal_next = 0;

@@ -1,9 +1,11 @@
-// Internal interface between the C ABI (c_abi.cpp) and the gfx950 kernels (sweep_kernels.hip).
+// Internal interface between the host units of the library (sweep_launch.cpp, resident.cpp, cost.cpp,
+// icp.cpp, lm.cpp) and the gfx950 kernels (sweep_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include "aql.hpp"
 #include "dispatch.hpp"
+#include "sweep_choice.hpp"  // forwardStepThreshold: one rule for the blocking calls and the step kernel
 
 #include <cstdint>
 
@@ -255,18 +257,6 @@ struct LmControl {  // device memory; written by the step kernel only
 constexpr int kLmControlBlocks = 2;
 constexpr int kLmGateMoments = 1;
 constexpr int kLmGateMomentsForm = 0, kLmGateLiteralForm = 1, kLmGateStopped = 2;
-
-// Below which |x_j| forward differences are evaluated literally: 0.08 where the warped cloud lies
-// within rho = 30 of the origin (where it was measured), growing with rho = (bound of |p| stored when
-// the data was laid out) + |t| beyond — the reference's noise is eps rho / h_j (derivation at c_abi.cpp
-// hasSmallForwardStep).  One rule for the blocking calls and the step kernel.
-#if defined(__HIPCC__) || defined(__CUDACC__)
-__host__ __device__
-#endif
-inline double forwardStepThreshold(double rho) {
-  const double scale = rho * (1.0 / 30.0);
-  return 0.08 * (scale > 1.0 ? scale : 1.0);
-}
 
 struct LmCostDesc {
   int model = 0;     // LmModel

@@ -1050,7 +1050,7 @@ __global__ void relayoutP2PKernel(const S *__restrict__ src, const S *__restrict
 }
 
 // Bounding box of the sources, once per data set: the scale the choice between the moments and the
-// literal evaluation depends on (c_abi.cpp leftBasisCancels, hasSmallForwardStep).  Every index is below
+// literal evaluation depends on (sweep_choice.hpp leftBasisCancels, hasSmallForwardStep).  Every index is below
 // `count`, so inside the tiles; a wavefront reduces with shuffles and its first lane takes the six
 // atomics on ordered keys (sweep.hpp sourceBoxKey).
 template <typename S>

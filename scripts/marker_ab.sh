@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of the library's command-batch bound (MOPT_MARKER_EVERY, c_abi.cpp boundCommandBatch): steady-state
+# A/B of the library's command-batch bound (MOPT_MARKER_EVERY, blocking.cpp boundCommandBatch): steady-state
 # step times and the steps after a synchronisation, same box, same process layout.
 for every in 1000000000 8 32 128; do
   echo "##### MOPT_MARKER_EVERY=$every"

@@ -1,7 +1,8 @@
 // Host-side logic of the drop-in, without a GPU and without the HIP library: the LM caller's
 // status / error behaviour (levenberg_marquadt_dyn.cpp:34-119, optimizer.h:26-54), the pivoted
 // LDL^T it solves with, the dense matrix subset, SO(3) exp / log, loss weights, the logger and
-// the exception type.  Costs here are tiny closed-form CostFunctionBase subclasses written for
+// the exception type; and the library's host-only headers (csrc/dispatch.hpp, csrc/sweep_choice.hpp: the
+// rules that choose a sweep).  Costs here are tiny closed-form CostFunctionBase subclasses written for
 // the test; nothing from oracle/ or the device path is involved.
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <type_traits>
 
 #include "dispatch.hpp"
+#include "sweep_choice.hpp"
 #include "moptimizer_amd/cost_function_hip.hpp"
 #include "moptimizer_caller/levenberg_marquadt.hpp"
 #include "moptimizer_amd/so3.hpp"
@@ -429,9 +431,125 @@ static void dispatchPrimitives() {
     }
 }
 
+// csrc/sweep_choice.hpp: the rules that decide which sweep runs, at the values their comments state.
+// Expected values are worked out here from those formulas, never by calling a rule twice.
+static void sweepChoiceRules() {
+  namespace choice = mopt::choice;
+  // forward differences: literal where some |x_j| (0 judged as 1) is below 0.08 max(1, rho / 30),
+  // rho = src_bound + |t|.  Here |t| = |(1, 2, 2)| = 3 and src_bound = 10: rho = 13, threshold 0.08.
+  {
+    double x[6] = {1, 2, 2, 0.5, 0.5, 0.079};
+    expectTrue("forward step, rho <= 30: |x_j| = 0.079 is small", choice::hasSmallForwardStep(10.0, x));
+    x[5] = -0.079;
+    expectTrue("forward step, rho <= 30: x_j = -0.079 is small", choice::hasSmallForwardStep(10.0, x));
+    x[5] = 0.081;
+    expectTrue("forward step, rho <= 30: |x_j| = 0.081 is not", !choice::hasSmallForwardStep(10.0, x));
+    x[5] = 0.0;
+    expectTrue("forward step, rho <= 30: x_j = 0 is judged as 1, not small", !choice::hasSmallForwardStep(10.0, x));
+    x[5] = 0.079;
+    expectTrue("forward step: rho = 27 + 3 = 30 still has the threshold 0.08", choice::hasSmallForwardStep(27.0, x));
+    x[5] = 0.081;
+    expectTrue("forward step: rho = 30, 0.081 is not small", !choice::hasSmallForwardStep(27.0, x));
+  }
+  // rho = 300: threshold 0.08 * 300 / 30 = 0.8
+  expectNear("forwardStepThreshold(300)", mopt::forwardStepThreshold(300.0), 0.8, 1e-15);
+  expectNear("forwardStepThreshold(30)", mopt::forwardStepThreshold(30.0), 0.08, 0);
+  expectNear("forwardStepThreshold(3)", mopt::forwardStepThreshold(3.0), 0.08, 0);
+  expectNear("forwardStepThreshold(3000)", mopt::forwardStepThreshold(3000.0), 8.0, 1e-14);
+  {
+    double x[6] = {0, 0, 0, 2, 2, 0.79};
+    expectTrue("forward step, bound 300: 0.79 < 0.8 is small", choice::hasSmallForwardStep(300.0, x));
+    x[5] = 0.81;
+    expectTrue("forward step, bound 300: 0.81 is not (and the zeros are judged as 1 > 0.8)",
+               !choice::hasSmallForwardStep(300.0, x));
+    const double zero[6] = {0, 0, 0, 0, 0, 0};
+    expectTrue("forward step, bound 300: all-zero x is not small (1 > 0.8)", !choice::hasSmallForwardStep(300.0, zero));
+    expectTrue("forward step, bound 3000: all-zero x is small (1 < 8)", choice::hasSmallForwardStep(3000.0, zero));
+    // the |t| term: src_bound = 295 alone gives 0.08 * 295 / 30 = 0.7867 < 0.79; |t| = |(3, 4, 0)| = 5
+    // brings rho to 300 and the threshold to 0.8 > 0.79
+    const double still[6] = {0, 0, 0, 2, 2, 0.79}, moved[6] = {3, 4, 0, 2, 2, 0.79};
+    expectTrue("forward step, bound 295 and t = 0: 0.79 > 0.7867 is not small", !choice::hasSmallForwardStep(295.0, still));
+    expectTrue("forward step, bound 295 and |t| = 5: 0.79 < 0.8 is small", choice::hasSmallForwardStep(295.0, moved));
+  }
+  // the left-perturbation basis cancels where |t|^2 > 1e3 rho_w^2, rho_w = |R c0 + t| + r
+  {
+    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, c0[3] = {1000, 0, 0};
+    const double back[3] = {-1000, 0, 0}, none[3] = {0, 0, 0};
+    expectTrue("leftBasisCancels: t = -c0, rho_w = 1, |t|^2 = 1e6 > 1e3", choice::leftBasisCancels(c0, 1.0, I, back));
+    expectTrue("leftBasisCancels: t = 0 does not (0 > 1e3 * 1001^2 is false)", !choice::leftBasisCancels(c0, 1.0, I, none));
+    // t = (-1000, y, 0): rho_w = y + 1, |t|^2 = 1e6 + y^2.  y = 30: 1000900 > 961000; y = 31: 1000961 < 1024000
+    const double y30[3] = {-1000, 30, 0}, y31[3] = {-1000, 31, 0};
+    expectTrue("leftBasisCancels: 1000900 > 1e3 * 31^2", choice::leftBasisCancels(c0, 1.0, I, y30));
+    expectTrue("leftBasisCancels: 1000961 < 1e3 * 32^2", !choice::leftBasisCancels(c0, 1.0, I, y31));
+    // a quarter turn about z maps c0 = (1000, 0, 0) to (0, 1000, 0): it is R c0 + t that counts
+    const double Rz[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1}, back_y[3] = {0, -1000, 0};
+    expectTrue("leftBasisCancels: R c0 + t = 0 under a rotation", choice::leftBasisCancels(c0, 1.0, Rz, back_y));
+    expectTrue("leftBasisCancels: the same t without the rotation (rho_w = 1000 sqrt 2 + 1)",
+               !choice::leftBasisCancels(c0, 1.0, I, back_y));
+    // may cancel at some pose only where |c0|^2 > 1e3 r^2: sqrt(1000) = 31.62
+    const double c31[3] = {31, 0, 0}, c32[3] = {0, 0, -32}, c62[3] = {0, 62, 0}, c64[3] = {0, 64, 0};
+    expectTrue("leftBasisMayCancel: |c0| = 31 r does not", !choice::leftBasisMayCancel(c31, 1.0));
+    expectTrue("leftBasisMayCancel: |c0| = 32 r does", choice::leftBasisMayCancel(c32, 1.0));
+    expectTrue("leftBasisMayCancel: |c0| = 31 r, r = 2", !choice::leftBasisMayCancel(c62, 2.0));
+    expectTrue("leftBasisMayCancel: |c0| = 32 r, r = 2", choice::leftBasisMayCancel(c64, 2.0));
+  }
+  // usesMoments / residentPerIterate: rows AUTO, LITERAL, MOMENTS, MOMENTS_ALWAYS (the values 0..3 of the
+  // header); columns ANALYTIC, ANALYTIC_TST_LAYOUT, NUMERIC, ANALYTIC_LEFT, ANALYTIC_RIGHT (0..4)
+  static_assert(MOPT_KERNEL_AUTO == 0 && MOPT_KERNEL_LITERAL == 1 && MOPT_KERNEL_MOMENTS == 2 &&
+                    MOPT_KERNEL_MOMENTS_ALWAYS == 3 && MOPT_JAC_ANALYTIC == 0 && MOPT_JAC_ANALYTIC_TST_LAYOUT == 1 &&
+                    MOPT_JAC_NUMERIC == 2 && MOPT_JAC_ANALYTIC_LEFT == 3 && MOPT_JAC_ANALYTIC_RIGHT == 4,
+                "the order of the tables below");
+  static const bool moments_p2p_may_cancel[4][5] = {{1, 1, 1, 0, 1}, {0, 0, 0, 0, 0}, {1, 1, 1, 0, 1}, {1, 1, 1, 1, 1}};
+  static const bool moments_p2p_near[4][5] = {{1, 1, 1, 1, 1}, {0, 0, 0, 0, 0}, {1, 1, 1, 1, 1}, {1, 1, 1, 1, 1}};
+  // another model never takes the left-basis exception, whatever its sources' sphere says
+  static const bool moments_other[4][5] = {{1, 1, 1, 1, 1}, {0, 0, 0, 0, 0}, {1, 1, 1, 1, 1}, {1, 1, 1, 1, 1}};
+  static const bool per_iterate_p2p[4][5] = {{0, 0, 1, 0, 0}, {0, 0, 0, 0, 0}, {0, 0, 1, 0, 0}, {0, 0, 0, 0, 0}};
+  bool moments_ok = true, per_iterate_ok = true, switched_off_ok = true;
+  for (int variant = 0; variant < 4; ++variant)
+    for (int jac = 0; jac < 5; ++jac)
+      for (int may_cancel = 0; may_cancel < 2; ++may_cancel)
+        for (int p2p = 0; p2p < 2; ++p2p) {
+          const bool want_moments = !p2p ? moments_other[variant][jac]
+                                         : (may_cancel ? moments_p2p_may_cancel : moments_p2p_near)[variant][jac];
+          if (choice::usesMoments(p2p, variant, jac, may_cancel) != want_moments) {
+            moments_ok = false;
+            std::printf("  usesMoments(p2p=%d, variant=%d, jac=%d, may_cancel=%d) != %d\n", p2p, variant, jac,
+                        may_cancel, int(want_moments));
+          }
+          const bool want_per_iterate = p2p && per_iterate_p2p[variant][jac];
+          if (choice::residentPerIterate(p2p, variant, jac, true) != want_per_iterate) {
+            per_iterate_ok = false;
+            std::printf("  residentPerIterate(p2p=%d, variant=%d, jac=%d) != %d\n", p2p, variant, jac,
+                        int(want_per_iterate));
+          }
+          if (choice::residentPerIterate(p2p, variant, jac, false)) switched_off_ok = false;
+        }
+  expectTrue("usesMoments: the whole table (variant x jac_mode x may cancel x model)", moments_ok);
+  expectTrue("residentPerIterate: the whole table", per_iterate_ok);
+  expectTrue("residentPerIterate: never with MOPT_LM_PER_ITERATE off", switched_off_ok);
+  // speculation pays while fewer than two kept results went unused, or no more unused than used
+  {
+    const int unused[4] = {1, 2, 2, 3}, used[4] = {0, 2, 1, 2};
+    const bool pays[4] = {true, true, false, false};
+    for (int k = 0; k < 4; ++k) {
+      expectTrue("speculationPays, not free: (1,0) (2,2) pay, (2,1) (3,2) do not",
+                 choice::speculationPays(false, unused[k], used[k]) == pays[k]);
+      expectTrue("speculationPays, free: always", choice::speculationPays(true, unused[k], used[k]));
+    }
+  }
+  // gridFor: num_cus * blocks_per_cu, clamped to the tiles, to max_grid, and to at least 1
+  expectTrue("gridFor: 256 CUs x 2 with room", choice::gridFor(256, 2, 19532, 4096) == 512);
+  expectTrue("gridFor: clamped to num_tiles", choice::gridFor(256, 2, 17, 4096) == 17);
+  expectTrue("gridFor: clamped to max_grid", choice::gridFor(256, 32, 19532, 4096) == 4096);
+  expectTrue("gridFor: tiles below max_grid below the product", choice::gridFor(256, 32, 5000, 4096) == 4096);
+  expectTrue("gridFor: no tile still launches one workgroup", choice::gridFor(256, 1, 0, 4096) == 1);
+  expectTrue("gridFor: no overflow in num_cus * blocks_per_cu", choice::gridFor(1 << 20, 1 << 20, 1000, 4096) == 1000);
+}
+
 int main() {
   optimizerStatuses();
   dispatchPrimitives();
+  sweepChoiceRules();
   ldlt();
   denseAndSo3();
   lossThresholdRecovery();

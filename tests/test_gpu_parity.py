@@ -221,7 +221,7 @@ def exp_curve_float_linearize(t, y, x, loss):
 @pytest.mark.parametrize("kind", ["exp_curve", "rational"])
 def test_ragged_sizes_scalar_models(hip_lib, oracle, kind, dtype):
     """The built-in scalar models: a workgroup takes 256 packs of 16 bytes (512 fp64 / 1024 fp32
-    elements, c_abi.cpp scalarGrid); counts around a pack, a wavefront and that tile.  Tolerances of
+    elements, sweep_launch.cpp scalarGrid); counts around a pack, a wavefront and that tile.  Tolerances of
     test_small_parametric_models_match_oracle."""
     tile = 256 * (16 // np.dtype(dtype).itemsize)
     rng = np.random.default_rng(14)
