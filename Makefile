@@ -17,33 +17,34 @@ LIB         = $(LIBDIR)/libmoptimizer_hip.so
 
 PUBLIC_HEADERS = include/moptimizer_hip.h include/moptimizer_amd/so3.hpp $(CSRC)/sweep.hpp $(CSRC)/fd_device.hpp \
                  $(CSRC)/sweep_device.hpp $(CSRC)/jit_model.hpp $(CSRC)/cost_state.hpp $(CSRC)/lm_device.hpp $(CSRC)/aql.hpp \
-                 $(CSRC)/dispatch.hpp $(CSRC)/sweep_choice.hpp
+                 $(CSRC)/dispatch.hpp $(CSRC)/sweep_choice.hpp $(CSRC)/publish_device.hpp
 
 all: $(LIB)
 
 $(OBJDIR) $(LIBDIR):
 	mkdir -p $@
 
-# leading scalar kernel arguments preloaded into SGPRs at wave launch (gfx940+)
-$(OBJDIR)/sweep_kernels.o: $(CSRC)/sweep_kernels.hip $(PUBLIC_HEADERS) | $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -mllvm -amdgpu-kernarg-preload-count=4 -c $< -o $@
+# One code object per device unit; the host units are compiled as HIP too.
+DEVICE_UNITS = sweep_kernels finalize_kernels icp_match layout_kernels fd_kernels icp_grid lm_kernels
+HOST_UNITS   = c_abi cost sweep_launch blocking resident icp group aql jit_model device_pool combine lm
+OBJS         = $(DEVICE_UNITS:%=$(OBJDIR)/%.o) $(HOST_UNITS:%=$(OBJDIR)/%.o)
 
+# leading scalar kernel arguments preloaded into SGPRs at wave launch (gfx940+): the sweeps and what
+# shares their argument conventions; icp_grid and lm_kernels are built without it
+PRELOAD = -mllvm -amdgpu-kernarg-preload-count=4
+$(OBJDIR)/sweep_kernels.o $(OBJDIR)/finalize_kernels.o $(OBJDIR)/icp_match.o $(OBJDIR)/layout_kernels.o: UNITFLAGS = $(PRELOAD)
 # forward-difference sweeps: without the SLP vectorizer (fd_kernels.hip says why)
-$(OBJDIR)/fd_kernels.o: $(CSRC)/fd_kernels.hip $(PUBLIC_HEADERS) | $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -mllvm -amdgpu-kernarg-preload-count=4 -fno-slp-vectorize -c $< -o $@
+$(OBJDIR)/fd_kernels.o: UNITFLAGS = $(PRELOAD) -fno-slp-vectorize
+
+$(OBJDIR)/%.o: $(CSRC)/%.hip $(PUBLIC_HEADERS) | $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) $(INCLUDES) $(UNITFLAGS) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(PUBLIC_HEADERS) | $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -x hip -c $< -o $@
 
-$(OBJDIR)/icp_grid.o: $(CSRC)/icp_grid.hip $(PUBLIC_HEADERS) | $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -c $< -o $@
-
-$(OBJDIR)/lm_kernels.o: $(CSRC)/lm_kernels.hip $(PUBLIC_HEADERS) | $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(INCLUDES) -c $< -o $@
-
-OBJS = $(OBJDIR)/sweep_kernels.o $(OBJDIR)/fd_kernels.o $(OBJDIR)/icp_grid.o $(OBJDIR)/c_abi.o $(OBJDIR)/cost.o \
-       $(OBJDIR)/sweep_launch.o $(OBJDIR)/blocking.o $(OBJDIR)/resident.o $(OBJDIR)/icp.o \
-       $(OBJDIR)/group.o $(OBJDIR)/aql.o $(OBJDIR)/jit_model.o $(OBJDIR)/device_pool.o $(OBJDIR)/combine.o $(OBJDIR)/lm.o $(OBJDIR)/lm_kernels.o
+# the list scripts/check_spills.py checks
+print-device-units:
+	@echo $(DEVICE_UNITS)
 
 $(LIB): $(OBJS) | $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -L$(ROCM)/lib -lrccl -lhiprtc -lhsa-runtime64 -lpthread -lrt \
@@ -59,4 +60,4 @@ clean:
 	rm -rf build $(LIBDIR) tests/cpp/_build
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle cpptests clean
+.PHONY: all oracle cpptests clean print-device-units

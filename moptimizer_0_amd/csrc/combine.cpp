@@ -3,8 +3,8 @@
 //   MOPT_COMBINE_HOST  one slot block in POSIX shared memory, registered with HIP in every rank;
 //   MOPT_COMBINE_PEER  one slot block per rank in uncached device memory, exported / opened as
 //                      hipIpcMemHandle (xGMI stores between the GPUs of a node).
-// The pushes and waits themselves are in the finalize kernels (sweep_kernels.hip: publishToHost,
-// peerCombine) and in blockingSweep (blocking.cpp).
+// The pushes and waits themselves are in the finalize kernels (finalize_kernels.hip over
+// publish_device.hpp: publishToHost, peerCombine) and in blockingSweep (blocking.cpp).
 #include "cost_state.hpp"
 
 #include <fcntl.h>

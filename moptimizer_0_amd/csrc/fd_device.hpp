@@ -2,7 +2,7 @@
 // (linearization.h:65-124 over tst/point2point.cpp:32-51): the arithmetic of one correspondence — seven
 // residuals, eighteen quotients, w J^T S J and w J^T S r entry by entry — and the accumulation over the
 // packs a lane is handed.  Shared by fd_kernels.hip (the streaming sweeps; its header comment says why the
-// arithmetic is spelled the way it is) and sweep_kernels.hip (the one-launch solve of small problems,
+// arithmetic is spelled the way it is) and finalize_kernels.hip (the one-launch solve of small problems,
 // which holds its correspondences in registers).  Anonymous namespace of the including translation unit.
 #pragma once
 

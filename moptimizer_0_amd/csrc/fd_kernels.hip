@@ -33,7 +33,7 @@ namespace {
 // parity with the CPU path (the quotient amplifies them by eps / h); the products that follow are
 // associated for the fewest instructions: S A once, w folded into S A, d and r.
 // (the per-point arithmetic — PointPair, the accumulate helpers, p2pForwardDiffRow / p2pForwardDiffBody — is in
-// fd_device.hpp: the one-launch solve of small problems in sweep_kernels.hip evaluates with it too)
+// fd_device.hpp: the one-launch solve of small problems in finalize_kernels.hip evaluates with it too)
 
 template <typename S, bool STREAMING, int COV, int HOME>
 __global__ __launch_bounds__(kBlockThreads) void p2pForwardDiffKernel(const S *tiles, int num_tiles,

@@ -1,7 +1,7 @@
 // Correspondence search entry points (mopt_icp_*): the step upstream of the sweep, i.e. what a
 // registration model's update(x) does before every linearization (model.h:24-26,
 // levenberg_marquadt_dyn.cpp:54).  Grid construction and search run on the GPU (icp_grid.hip,
-// icpMatchKernel in sweep_kernels.hip); this file is their host side.
+// icpMatchKernel in icp_match.hip); this file is their host side.
 #include "cost_state.hpp"
 
 #include <cmath>

@@ -1,6 +1,6 @@
 // Uniform-grid construction for the correspondence search, on the GPU.
 //
-// The grid that icpMatchKernel walks (sweep_kernels.hip) is built once per cloud pair:
+// The grid that icpMatchKernel walks (icp_match.hip) is built once per cloud pair:
 //   bounding box of the targets -> cell ids -> stable sort of (cell id, index) -> cell offsets ->
 //   targets gathered cell by cell (32-byte padded), sources gathered in cell order.
 // Everything O(points) runs on the device; the host only picks the grid resolution from the six

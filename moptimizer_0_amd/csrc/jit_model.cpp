@@ -67,7 +67,7 @@ struct __attribute__((aligned(16))) Pack {
 };
 
 // Per-thread accumulators -> one row of NACC doubles per workgroup through an LDS transpose (the
-// epilogue of the hand-written sweeps, sweep_kernels.hip blockReduceStore): every lane stores its
+// epilogue of the hand-written sweeps, sweep_device.hpp blockReduceStore): every lane stores its
 // values once, thread (k, part) adds the 4 waves x 8 lanes of value k whose lane index is = part
 // (mod 8), three xor-shuffles combine the parts.  Six shuffle steps per value through the CU's
 // single LDS crossbar cost several times as much.

@@ -1,7 +1,8 @@
 // mopt_lm_minimize: the Levenberg-Marquardt loop of src/levenberg_marquadt_dyn.cpp:34-119 with the
 // iteration resident on the device (step kernel: lm_kernels.hip; resident sweeps:
-// sweep_kernels.hip).  The host only queues launches a few trial points ahead of the device and
-// watches a progress word in mapped memory; it takes no decision and copies nothing per iteration.
+// sweep_kernels.hip; resident finalize kernels: finalize_kernels.hip).  The host only queues
+// launches a few trial points ahead of the device and watches a progress word in mapped memory; it
+// takes no decision and copies nothing per iteration.
 #include "cost_state.hpp"
 
 #include <chrono>
@@ -187,7 +188,7 @@ int mopt_lm_minimize(mopt_cost *const *costs, int num_costs, const int *jacobian
       1 + (long long)opt.max_iterations *
               ((opt.lm_max_iterations > 0 ? opt.lm_max_iterations : 1) + (problem.rematch ? 1 : 0));
   // One small point2point cost (a few tiles: the reference's own test sizes): the whole loop in one
-  // launch of one workgroup (sweep_kernels.hip p2pSolveSmallKernel) instead of two launches per
+  // launch of one workgroup (finalize_kernels.hip p2pSolveSmallKernel) instead of two launches per
   // evaluated point — the same sums added in another order, so the same iterates to rounding.
   // MOPT_LM_ONE_LAUNCH_TILES: the largest tile count that goes this way (default and maximum
   // solveSmallMaxTiles(); a tile is 512 fp64 / 1024 fp32 correspondences; 0 = never), read per call.

@@ -1,6 +1,6 @@
 // Device code of the device-resident Levenberg-Marquardt step (see lm_kernels.hip for what it does
 // and which reference lines it follows).  Included by lm_kernels.hip (the stand-alone step / init
-// kernel) and by sweep_kernels.hip, whose finalize kernels run the step in the same launch when
+// kernel) and by finalize_kernels.hip, whose finalize kernels run the step in the same launch when
 // they belong to the last cost of a problem.  Everything here is in an anonymous namespace of the
 // including translation unit.
 #pragma once

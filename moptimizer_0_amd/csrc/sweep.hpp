@@ -1,5 +1,6 @@
 // Internal interface between the host units of the library (sweep_launch.cpp, resident.cpp, cost.cpp,
-// icp.cpp, lm.cpp) and the gfx950 kernels (sweep_kernels.hip).
+// icp.cpp, lm.cpp) and the gfx950 kernels (sweep_kernels.hip, fd_kernels.hip, finalize_kernels.hip,
+// icp_match.hip, layout_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -316,7 +317,7 @@ template <typename Args>
 hipError_t launchStoreArgs(const Args &value, Args *d_dst, hipStream_t stream);
 
 // A whole minimisation of one small point2point cost (moments sweep, <= solveSmallMaxTiles() tiles,
-// 6 parameters) in one launch of one workgroup: sweep_kernels.hip p2pSolveSmallKernel.  The cost's
+// 6 parameters) in one launch of one workgroup: finalize_kernels.hip p2pSolveSmallKernel.  The cost's
 // resident blocks must hold its data / loss / covariance (residentPrepare); the report goes where
 // problem.report says, as from the launch-per-point loop.  fd_cov: the cost's covariance form (kCov*) where
 // problem.fd_per_iterate is set — the kernel then also holds the literal forward-difference form for that

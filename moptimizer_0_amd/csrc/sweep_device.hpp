@@ -1,4 +1,5 @@
-// Device-side building blocks shared by the sweep kernels (sweep_kernels.hip, fd_kernels.hip):
+// Device-side building blocks shared by the sweep kernels (sweep_kernels.hip, fd_kernels.hip,
+// finalize_kernels.hip, icp_match.hip):
 // 16-byte lane loads, the ping-pong tile walk and the LDS-transpose workgroup reduction.  Everything
 // is in an anonymous namespace of the including translation unit.
 #pragma once

@@ -23,7 +23,6 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-DEVICE_SOURCES = ("sweep_kernels", "fd_kernels", "icp_grid", "lm_kernels")
 # Known and accepted: (kernel-name prefix, most scalar registers it may spill, why).  Nothing here may
 # spill a VGPR or use scratch, and every kernel that streams data per element must stay off this list.
 ACCEPTED_SGPR_SPILLS = (
@@ -58,6 +57,13 @@ ACCEPTED_AGPR_RESIDENT = (
     ("mopt::p2pSolveSmallKernel<", 32),  # (0 since n is fixed at compile time; 20-28 before)
 )
 FIELDS = ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")
+
+
+def device_sources():
+    """The Makefile's own list of device units (so a unit added there is checked here)."""
+    out = subprocess.check_output(["make", "-C", ROOT, "-s", "--no-print-directory", "print-device-units"],
+                                  text=True)
+    return out.split()
 
 
 def compile_command(stem):
@@ -158,8 +164,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--table", action="store_true", help="print every kernel, not only offenders")
     ap.add_argument("--only", default="", help="substring filter on the demangled kernel name")
-    ap.add_argument("--sources", nargs="*", default=list(DEVICE_SOURCES))
+    ap.add_argument("--sources", nargs="*", default=None, help="device units (default: the Makefile's list)")
     args = ap.parse_args()
+    if args.sources is None:
+        args.sources = device_sources()
     bad = total = accepted = 0
     with tempfile.TemporaryDirectory() as workdir:
         for stem in args.sources:

@@ -3,13 +3,17 @@
 // the sweep of one cost (40 k or 60 k elements: 157 / 235 tiles of 256, one per workgroup) between two marker
 // kernels on one stream, stamps read back after the last of many launches.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iinclude -Imoptimizer_0_amd/csrc \
-//         -mllvm -amdgpu-kernarg-preload-count=4 scripts/probes/reproj_stamps.cpp -o /tmp/reproj_stamps
+//         -mllvm -amdgpu-kernarg-preload-count=4 scripts/probes/reproj_stamps.cpp -o /tmp/reproj_stamps \
+//         -lhsa-runtime64
 //   /tmp/reproj_stamps [elements]
 // Stamp k of a workgroup (wave 0):  0 entry | 1 tile + constants arrived | 2 residual at x |
 // 3 six perturbed residuals, twelve quotients | 4 accumulated | 5 (= 4 for one tile) | 6 row stored
 #define MOPT_STAMP_WORDS 8
 #include "../../moptimizer_0_amd/csrc/sweep_kernels.hip"
-#include "../../moptimizer_0_amd/csrc/fd_kernels.hip"  // (only to resolve what the first refers to)
+#include "../../moptimizer_0_amd/csrc/layout_kernels.hip"  // launchRelayoutReproj
+// (only to resolve what the first refers to: the forward-difference launchers, the direct dispatch)
+#include "../../moptimizer_0_amd/csrc/fd_kernels.hip"
+#include "../../moptimizer_0_amd/csrc/aql.cpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -136,12 +140,13 @@ int main(int argc, char **argv) {
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL(emptyKernel<256>, g, dim3(256), 0, nullptr, a, b, 0, d_partials); }, e0, e1),
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL(emptyKernel<512>, g, dim3(512), 0, nullptr, a, b, 0, d_partials); }, e0, e1),
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL(loadOnlyKernel, g, dim3(256), 0, nullptr, a, b, 0, args); }, e0, e1));
-    std::printf("  workgroup reduction alone: 1 value %.2f  23 values %.2f  28 values %.2f  43 values %.2f  28 values, 512 threads %.2f\n",
+    // (28 values over 512 threads, measured in round 4, no longer instantiates: blockReduceStore's
+    // one-pass form of up to 32 values asserts that a workgroup stays within half a CU's LDS)
+    std::printf("  workgroup reduction alone: 1 value %.2f  23 values %.2f  28 values %.2f  43 values %.2f\n",
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<1, 256>), g, dim3(256), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1),
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<23, 256>), g, dim3(256), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1),
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<28, 256>), g, dim3(256), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1),
-                dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<43, 256>), g, dim3(256), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1),
-                dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<28, 512>), g, dim3(512), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1));
+                dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reduceOnlyKernel<43, 256>), g, dim3(256), 0, nullptr, a, b, 0, d_partials, 1.5); }, e0, e1));
     std::printf("  cost-only sweep %.2f\n",
                 dispatchMicroseconds([&](hipEvent_t a, hipEvent_t b) { hipExtLaunchKernelGGL((reprojKernel<kCovIdentity, true>), g, dim3(256), 0, nullptr, a, b, 0, args); }, e0, e1));
   }

@@ -797,7 +797,7 @@ def test_four_wide_costs_each_with_full_rows(hip_lib):
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_small_problems_in_one_launch_take_the_same_iterates(hip_lib, oracle, dtype, monkeypatch):
     """One point2point cost of at most four tiles (the reference's own sizes) is minimised by ONE
-    launch of one workgroup (sweep_kernels.hip p2pSolveSmallKernel: correspondences held in registers;
+    launch of one workgroup (finalize_kernels.hip p2pSolveSmallKernel: correspondences held in registers;
     sweep, contraction and LM step without leaving the kernel).  Against the launch-per-point loop
     (MOPT_LM_ONE_LAUNCH_TILES=0), whose sums it adds in another order: truncated after k outer
     iterations the same status, iteration count, sweeps and — to rounding — x and cost, for every
