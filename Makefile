@@ -26,7 +26,7 @@ $(OBJDIR) $(LIBDIR):
 
 # One code object per device unit; the host units are compiled as HIP too.
 DEVICE_UNITS = sweep_kernels finalize_kernels icp_match layout_kernels fd_kernels icp_grid lm_kernels
-HOST_UNITS   = c_abi cost sweep_launch blocking resident icp group aql jit_model device_pool combine lm
+HOST_UNITS   = c_abi cost sweep_launch blocking resident icp group aql jit_model device_pool combine lm batch
 OBJS         = $(DEVICE_UNITS:%=$(OBJDIR)/%.o) $(HOST_UNITS:%=$(OBJDIR)/%.o)
 
 # leading scalar kernel arguments preloaded into SGPRs at wave launch (gfx940+): the sweeps and what

@@ -503,6 +503,71 @@ MOPT_API int mopt_lm_minimize(mopt_cost *const *costs, int num_costs, const int 
  * cost was created: the points so evaluated, and how many of them took the literal sweep. */
 MOPT_API int mopt_cost_lm_choice_stats(const mopt_cost *cost, int64_t *points, int64_t *literal_points);
 
+/* ---- a batch of small registrations in one launch -------------------------------------------
+ *
+ * Small registrations rarely come alone: one per tracked object, per scan segment or submap pair,
+ * per start pose of a multi-start, per hypothesis of a consensus loop.  A `mopt_batch` holds B
+ * independent small point2point problems — B times the `Point2Point` model bound to its two clouds
+ * plus its cost (tst/point2point.cpp:24-29,82-83), each with an optimizer of its own
+ * (include/moptimizer/optimizer.h:58, src/levenberg_marquadt_dyn.cpp:34-119) — laid out once and
+ * minimised together: ONE launch of B workgroups, a problem per workgroup, each running the
+ * one-launch solve mopt_lm_minimize gives a lone small cost.  Every problem has its own x, LM
+ * state, report and stopping decision; nothing crosses workgroups, and a problem computes what
+ * its lone solve computes (the same device code over the same sums in the same order).
+ *
+ * mopt_point2point_batch_create   B x (the model object + its cost-class constructor,
+ *                                 tst/point2point.cpp:24-29,82-83).  src_xyz / tgt_xyz: the packed
+ *                                 xyz of all problems behind one another (host or device memory:
+ *                                 flags as mopt_create_flags); offsets[B + 1] (host): problem i
+ *                                 owns correspondences [offsets[i], offsets[i + 1]).  A NULL
+ *                                 pointer, num_problems < 1, a scalar_bytes other than 4 or 8,
+ *                                 unknown flag bits, offsets that do not start at 0 or decrease,
+ *                                 and an empty problem are MOPT_ERR_INVALID_ARGUMENT; a problem of
+ *                                 more than four tiles (2048 fp64 / 4096 fp32 correspondences) is
+ *                                 MOPT_ERR_UNSUPPORTED and mopt_last_error() names its index and
+ *                                 size — all before a device is looked for.
+ * mopt_batch_destroy              ~CostFunctionBase x B        include/moptimizer/cost_function.h:35
+ * mopt_batch_set_covariance       CostFunctionBase::setCovariance (cost_function.h:38-40), one for
+ *                                 the batch; 3 x 3 column-major in the batch's scalar, NULL = I
+ * mopt_batch_set_loss             CostFunctionBase::setLossFunction (cost_function.h:37), one for
+ *                                 the batch
+ * mopt_batch_lm_minimize          LevenbergMarquadtDynamic<Scalar>::minimize
+ *                                 (src/levenberg_marquadt_dyn.cpp:34-119) of every problem.
+ *                                 x: num_problems x 6 scalars, a row per problem, start poses in,
+ *                                 results out; reports: num_problems of them (may be NULL);
+ *                                 options as in mopt_lm_minimize (`window` does not apply;
+ *                                 max_iterations == 0 and lm_max_iterations == 0 as there; at most
+ *                                 4096 evaluated points a problem).  Evaluation is
+ *                                 MOPT_KERNEL_AUTO's: moments for the analytic modes, and under
+ *                                 MOPT_JAC_NUMERIC the choice per evaluated point between moments
+ *                                 and the literal forward-difference form, taken by each workgroup
+ *                                 for its own problem at its own x with its own source bound.
+ *                                 MOPT_JAC_ANALYTIC_LEFT over a problem whose sources lie far from
+ *                                 their frame's origin (|c0|^2 > 1e3 r^2: the lone solve sweeps
+ *                                 such a cost literally, launch per point) is refused with
+ *                                 MOPT_ERR_UNSUPPORTED, naming the first such problem; the batch is
+ *                                 unchanged by a refused call.  The host takes no decision and
+ *                                 copies nothing per iteration; a fault on the batch's stream
+ *                                 comes back as MOPT_ERR_HIP.
+ * mopt_batch_lm_choice_stats      mopt_cost_lm_choice_stats summed over the problems
+ *
+ * A batch is used by one thread at a time; it owns one stream and none of the direct-dispatch
+ * queues. */
+typedef struct mopt_batch mopt_batch;
+MOPT_API int mopt_point2point_batch_create(mopt_batch **out, int device, int scalar_bytes,
+                                           const void *src_xyz, const void *tgt_xyz,
+                                           const int64_t *offsets, int num_problems, int flags);
+MOPT_API int mopt_batch_destroy(mopt_batch *batch);
+MOPT_API int mopt_batch_info(const mopt_batch *batch, int *num_problems, int64_t *total_count,
+                             int *scalar_bytes);
+MOPT_API int mopt_batch_set_covariance(mopt_batch *batch, const void *cov_colmajor);
+MOPT_API int mopt_batch_set_loss(mopt_batch *batch, int loss_kind, double parameter);
+MOPT_API int mopt_batch_lm_minimize(mopt_batch *batch, int jacobian_mode, void *x,
+                                    const mopt_lm_options *options /* NULL = defaults */,
+                                    mopt_lm_report *reports /* num_problems, may be NULL */);
+MOPT_API int mopt_batch_lm_choice_stats(const mopt_batch *batch, int64_t *points,
+                                        int64_t *literal_points);
+
 /* ---- measurement -------------------------------------------------------------------------- */
 
 /* With profiling on, sweep kernel launches are bracketed by HIP events recorded on their stream:

@@ -25,6 +25,7 @@ from ._capi import (  # noqa: F401
     IcpCost,
     JitModelCost,
     MoptError,
+    Point2PointBatch,
     Point2PointCost,
     Point2PointGroup,
     ReprojectionCost,

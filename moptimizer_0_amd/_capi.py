@@ -127,6 +127,18 @@ def load():
         "mopt_lm_minimize": [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
                              ctypes.POINTER(ctypes.c_int), ctypes.c_void_p,
                              ctypes.POINTER(LmOptions), ctypes.POINTER(LmReport)],
+        "mopt_point2point_batch_create": [c_void_pp, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
+                                          ctypes.c_int],
+        "mopt_batch_destroy": [ctypes.c_void_p],
+        "mopt_batch_info": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
+                            ctypes.POINTER(ctypes.c_int)],
+        "mopt_batch_set_covariance": [ctypes.c_void_p, ctypes.c_void_p],
+        "mopt_batch_set_loss": [ctypes.c_void_p, ctypes.c_int, ctypes.c_double],
+        "mopt_batch_lm_minimize": [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                   ctypes.POINTER(LmOptions), ctypes.POINTER(LmReport)],
+        "mopt_batch_lm_choice_stats": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64)],
         "mopt_cost_set_profiling": [ctypes.c_void_p, ctypes.c_int],
         "mopt_cost_profile": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_int64)],
@@ -468,6 +480,73 @@ class Point2PointCost(_CostBase):
         check(load().mopt_point2point_set_data(self._h, _ptr(src), _ptr(tgt), src.shape[0],
                                                INPUT_HOST))
         self.count = src.shape[0]
+
+
+class Point2PointBatch:
+    """B independent small point-to-point problems laid out once and minimised together in one launch
+    (mopt_batch).  srcs / tgts: two lists of (n_i, 3) host arrays, at most four tiles each."""
+
+    def __init__(self, srcs, tgts, device=0, dtype=np.float64):
+        self._h = ctypes.c_void_p()
+        self.scalar_bytes = np.dtype(dtype).itemsize
+        srcs = [np.ascontiguousarray(s, dtype=dtype).reshape(-1, 3) for s in srcs]
+        tgts = [np.ascontiguousarray(t, dtype=dtype).reshape(-1, 3) for t in tgts]
+        assert len(srcs) == len(tgts) and all(s.shape == t.shape for s, t in zip(srcs, tgts))
+        self.num_problems = len(srcs)
+        self.counts = [s.shape[0] for s in srcs]
+        offsets = np.zeros(self.num_problems + 1, dtype=np.int64)
+        offsets[1:] = np.cumsum(self.counts)
+        src = np.concatenate(srcs) if srcs else np.zeros((0, 3), dtype=dtype)
+        tgt = np.concatenate(tgts) if tgts else np.zeros((0, 3), dtype=dtype)
+        check(load().mopt_point2point_batch_create(
+            ctypes.byref(self._h), device, self.scalar_bytes, _ptr(src), _ptr(tgt),
+            offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self.num_problems, INPUT_HOST))
+
+    def set_covariance(self, cov):
+        """One covariance for the batch (3 x 3; None = identity)."""
+        if cov is None:
+            check(load().mopt_batch_set_covariance(self._h, None))
+            return
+        cov = np.asfortranarray(np.asarray(cov, dtype=_dtype_of(self.scalar_bytes)))
+        assert cov.shape == (3, 3)
+        check(load().mopt_batch_set_covariance(self._h, _ptr(cov)))
+
+    def set_loss(self, kind, parameter=0.0):
+        check(load().mopt_batch_set_loss(self._h, int(kind), float(parameter)))
+
+    def minimize(self, x0s, jac_mode, max_iterations=15, lm_max_iterations=3, manifold=False):
+        """LevenbergMarquadtDynamic::minimize of every problem from its row of x0s (B x 6).  `manifold` as
+        in lm_minimize.  Returns (xs, [report dict per problem])."""
+        manifold = {"left": 1, "right": 2}.get(manifold, manifold)
+        xs = np.array(x0s, dtype=_dtype_of(self.scalar_bytes)).reshape(self.num_problems, 6).copy()
+        opt = LmOptions(int(max_iterations), int(lm_max_iterations), int(manifold), 0)
+        reps = (LmReport * self.num_problems)()
+        check(load().mopt_batch_lm_minimize(self._h, int(jac_mode), _ptr(xs), ctypes.byref(opt), reps))
+        return xs, [dict(status=r.status, iterations=r.iterations, sweeps=r.sweeps, cost=r.cost,
+                         lambda_=r.lambda_) for r in reps]
+
+    def lm_choice_stats(self):
+        """mopt_cost_lm_choice_stats summed over the problems: (points whose forward-difference form was
+        chosen on the device, how many of them took the literal one) since creation."""
+        points, literal = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(load().mopt_batch_lm_choice_stats(self._h, ctypes.byref(points), ctypes.byref(literal)))
+        return points.value, literal.value
+
+    def info(self):
+        n, total, sb = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
+        check(load().mopt_batch_info(self._h, ctypes.byref(n), ctypes.byref(total), ctypes.byref(sb)))
+        return dict(num_problems=n.value, total_count=total.value, scalar_bytes=sb.value)
+
+    def close(self):
+        if self._h:
+            load().mopt_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class IcpCost(Point2PointCost):

@@ -1,7 +1,7 @@
 // The small entry points of libmoptimizer_hip.so's C ABI (declared in include/moptimizer_hip.h): the
 // error string, version and device count, the SE(3) helpers, a cost's statistics, communicator, stream
 // and profiling.  The rest of the ABI lives with its subject: cost.cpp (lifetime and configuration),
-// blocking.cpp (the blocking and *_async sweeps), icp.cpp, group.cpp, combine.cpp, lm.cpp.  There is no
+// blocking.cpp (the blocking and *_async sweeps), icp.cpp, group.cpp, combine.cpp, lm.cpp, batch.cpp.  There is no
 // CPU implementation behind any entry point: when HIP cannot run the work the call returns an error code.
 #include "cost_state.hpp"
 

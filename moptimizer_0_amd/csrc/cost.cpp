@@ -138,21 +138,15 @@ namespace {
 constexpr size_t kBounceBytes = size_t(8) << 20;
 std::mutex g_bounce_mutex;
 void *g_bounce = nullptr;  // pinned, allocated on first use, kept for the life of the process
-
-// Copies (or adopts) two input arrays into device staging memory and returns device pointers.
-struct Staging {
-  void *a = nullptr, *b = nullptr;
-  void *block = nullptr;  // one allocation behind both copies
-  hipStream_t stream = nullptr;
-  ~Staging() {
-    if (!block) return;
-    (void)hipStreamSynchronize(stream);  // an early error return may leave a copy in flight
-    deviceRelease(block);
-  }
-};
 }  // namespace
 
-static int stageInputs(const void *ha, size_t bytes_a, const void *hb, size_t bytes_b, unsigned flags,
+Staging::~Staging() {
+  if (!block) return;
+  (void)hipStreamSynchronize(stream);  // an early error return may leave a copy in flight
+  deviceRelease(block);
+}
+
+int stageInputs(const void *ha, size_t bytes_a, const void *hb, size_t bytes_b, unsigned flags,
                 hipStream_t s, Staging &st) {
   if (flags & MOPT_INPUT_DEVICE) {
     st.a = const_cast<void *>(ha);

@@ -279,6 +279,19 @@ int commonCreate(mopt_cost *c, int device);
 hipError_t quiesceCost(mopt_cost *c);
 // quiesce, then give back everything the cost holds and the cost itself (NULL: nothing)
 void destroyCost(mopt_cost *c);
+// Two input arrays of a create call copied into device staging memory (small ones through the library's
+// pinned bounce buffer) — or adopted, under MOPT_INPUT_DEVICE: a / b are device pointers either way.
+struct Staging {
+  void *a = nullptr, *b = nullptr;
+  void *block = nullptr;  // one allocation behind both copies
+  hipStream_t stream = nullptr;
+  Staging() = default;
+  Staging(const Staging &) = delete;
+  Staging &operator=(const Staging &) = delete;
+  ~Staging();  // waits for `stream`, then gives the block back
+};
+int stageInputs(const void *ha, size_t bytes_a, const void *hb, size_t bytes_b, unsigned flags,
+                hipStream_t s, Staging &st);
 // H | b | sum_sq as doubles -> the caller's arrays in the cost's scalar type
 void storeResult(const mopt_cost *c, const double *res, void *hessian, void *b, void *sum_sq);
 

@@ -1,6 +1,7 @@
 // gfx950 kernels that turn the workgroup partials a sweep left into H | b | sum_sq and hand them
 // over (publish_device.hpp): the blocking calls' finalize kernels, the resident forms that take the
-// LM step in the same launch (lm_device.hpp), and the whole small minimisation in one launch.
+// LM step in the same launch (lm_device.hpp), and the whole small minimisation in one launch — of one
+// workgroup for a lone cost, of a workgroup per problem for a batch.
 #include "sweep_device.hpp"
 #include "fd_device.hpp"
 #include "lm_device.hpp"
@@ -388,11 +389,21 @@ constexpr int kSolveSmallTiles = 4;
 // covariance (fd_device.hpp, over the packs held in registers, rotations re-read from LDS: registers are
 // what this kernel is short of) and the step says per point which form runs — a cost that differentiates
 // numerically under MOPT_KERNEL_AUTO / _MOMENTS (LmProblem::fd_per_iterate).  FD_COV = -1: moments only.
-template <typename S, int FD_COV>
-__global__ __launch_bounds__(kBlockThreads) void p2pSolveSmallKernel(
-    const S *tiles, int num_tiles, const P2PSweepArgs<S> *__restrict__ d_args,
-    const AffineBasis *__restrict__ d_basis, double *result, const LmProblem problem,
-    const LmStart<S> start, int max_points) {
+//
+// The body of that kernel, shared by its two callers: p2pSolveSmallKernel (one problem, described by
+// kernel arguments) and p2pSolveBatchKernel (a problem per workgroup, described by per-batch arrays).
+// fill_problem(words): the caller's way of putting the problem's description into the LDS copy the loop
+// reads (the barrier that makes it visible to every thread is the one behind the copies of the argument
+// and basis blocks); `start` may lie in kernel arguments or in device memory.
+static_assert(sizeof(LmProblem) % 4 == 0, "copied by words");
+constexpr int kProblemWords = int(sizeof(LmProblem) / 4);
+
+template <typename S, int FD_COV, typename FillProblem>
+__device__ __forceinline__ void p2pSolveSmallBody(const S *tiles, int num_tiles,
+                                                  const P2PSweepArgs<S> *__restrict__ d_args,
+                                                  const AffineBasis *__restrict__ d_basis, double *result,
+                                                  FillProblem &&fill_problem, const LmStart<S> &start,
+                                                  int max_points) {
   constexpr bool kChooses = FD_COV >= 0;
   __shared__ int fd_choice;  // written by the step: the next point takes the literal form
   if (threadIdx.x == 0) fd_choice = 0;
@@ -401,10 +412,8 @@ __global__ __launch_bounds__(kBlockThreads) void p2pSolveSmallKernel(
   // the problem's description, read from LDS inside the loop: as kernel arguments its 1.2 KB are
   // loop invariants the compiler loads up front into scalar registers, of which there are 104 —
   // some 400 spills to vector lanes, read back one by one in every step
-  static_assert(sizeof(LmProblem) % 4 == 0, "copied by words");
-  __shared__ alignas(16) unsigned int problem_words[sizeof(LmProblem) / 4];
-  for (int i = threadIdx.x; i < int(sizeof(LmProblem) / 4); i += kBlockThreads)
-    problem_words[i] = reinterpret_cast<const unsigned int *>(&problem)[i];
+  __shared__ alignas(16) unsigned int problem_words[kProblemWords];
+  fill_problem(problem_words);
   const LmProblem &P = *reinterpret_cast<const LmProblem *>(problem_words);
   __shared__ double row[kAccMoments];
   __shared__ double own[kSlotData];
@@ -496,6 +505,71 @@ __global__ __launch_bounds__(kBlockThreads) void p2pSolveSmallKernel(
              tick_sweep - tick_step, num_tiles, tick_finalize - tick_sweep, wall_clock64() - tick_finalize);
 #endif
   }
+}
+
+template <typename S, int FD_COV>
+__global__ __launch_bounds__(kBlockThreads) void p2pSolveSmallKernel(
+    const S *tiles, int num_tiles, const P2PSweepArgs<S> *__restrict__ d_args,
+    const AffineBasis *__restrict__ d_basis, double *result, const LmProblem problem,
+    const LmStart<S> start, int max_points) {
+  p2pSolveSmallBody<S, FD_COV>(
+      tiles, num_tiles, d_args, d_basis, result,
+      [&](unsigned int *words) {
+        for (int i = threadIdx.x; i < kProblemWords; i += kBlockThreads)
+          words[i] = reinterpret_cast<const unsigned int *>(&problem)[i];
+      },
+      start, max_points);
+}
+
+// B independent small problems, one per workgroup (mopt_batch, batch.cpp): workgroup b runs the body
+// above over tiles [first_tile[b], first_tile[b + 1]) of the batch's tile array with its own argument,
+// basis, result, control and report blocks and its own start pose.  One description of the problem
+// serves the batch (options, Jacobian mode: device memory, written per call); each workgroup copies
+// it into LDS and patches what is its own — the pointers and the bound of |p| its forward-difference
+// choice is taken with — there, so that nothing per problem is held in registers across the loop.
+// Nothing crosses workgroups.
+static_assert(sizeof(LmStart<double>) == kMaxWideParams * sizeof(double) &&
+                  sizeof(LmStart<float>) == kMaxWideParams * sizeof(float),
+              "BatchSolveLaunch::starts is an array of these");
+static_assert(kBatchResultStride >= kResultDoubles, "a problem's H | b | sum_sq");
+template <typename S>
+struct SolveBatchArgs {
+  const S *tiles;
+  const int *first_tile;             // [B + 1]
+  const LmProblem *problem;          // the batch's one description (device memory)
+  P2PSweepArgs<S> *args;             // [B]
+  AffineBasis *basis;                // [B]
+  double *results;                   // [B][kBatchResultStride]
+  LmControl *controls;               // [B][kLmControlBlocks]
+  LmReport *reports;                 // [B], mapped host memory
+  const LmStart<S> *starts;          // [B]
+  const double *source_bounds;       // [B]: |centre| + radius of each problem's sources
+  int max_points;
+};
+
+template <typename S, int FD_COV>
+__global__ __launch_bounds__(kBlockThreads) void p2pSolveBatchKernel(const SolveBatchArgs<S> batch) {
+  const int b = blockIdx.x;
+  const int first = batch.first_tile[b];
+  p2pSolveSmallBody<S, FD_COV>(
+      batch.tiles + size_t(first) * TileShape<S>::kP2PScalars, batch.first_tile[b + 1] - first,
+      batch.args + b, batch.basis + b, batch.results + size_t(b) * kBatchResultStride,
+      [&](unsigned int *words) {
+        for (int i = threadIdx.x; i < kProblemWords; i += kBlockThreads)
+          words[i] = reinterpret_cast<const unsigned int *>(batch.problem)[i];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          LmProblem &P = *reinterpret_cast<LmProblem *>(words);
+          P.control = batch.controls + size_t(b) * kLmControlBlocks;
+          P.state = nullptr;  // (the state of a one-launch solve never leaves LDS)
+          P.report = batch.reports + b;
+          P.cost[0].args = batch.args + b;
+          P.cost[0].basis = batch.basis + b;
+          P.cost[0].result = batch.results + size_t(b) * kBatchResultStride;
+          P.fd_source_bound = batch.source_bounds[b];
+        }
+      },
+      batch.starts[b], batch.max_points);
 }
 
 __device__ __forceinline__ void finalizeCostBody(const double *partials, int grid, double *result,
@@ -620,6 +694,31 @@ template hipError_t launchP2PSolveSmall<float>(const float *, int, const P2PSwee
 template hipError_t launchP2PSolveSmall<double>(const double *, int, const P2PSweepArgs<double> *,
                                                 const AffineBasis *, double *, const LmProblem &,
                                                 const double *, int, int, hipStream_t);
+
+template <typename S>
+hipError_t launchP2PSolveBatch(const BatchSolveLaunch &launch, int fd_cov, hipStream_t stream) {
+  if (launch.num_problems < 1 || launch.max_points < 1) return hipErrorInvalidValue;
+  SolveBatchArgs<S> a;
+  a.tiles = static_cast<const S *>(launch.tiles);
+  a.first_tile = launch.first_tile;
+  a.problem = launch.problem;
+  a.args = static_cast<P2PSweepArgs<S> *>(launch.args);
+  a.basis = launch.basis;
+  a.results = launch.results;
+  a.controls = launch.controls;
+  a.reports = launch.reports;
+  a.starts = static_cast<const LmStart<S> *>(launch.starts);
+  a.source_bounds = launch.source_bounds;
+  a.max_points = launch.max_points;
+  auto go = [&](auto fd) {
+    return launchResident(p2pSolveBatchKernel<S, fd()>, launch.num_problems, stream, a);
+  };
+  if (launch.fd_per_iterate)
+    return dispatch::intOrFail<kCovIdentity, kCovSymmetric, kCovGeneral>(fd_cov, hipErrorInvalidValue, go);
+  return go(dispatch::Int<-1>{});
+}
+template hipError_t launchP2PSolveBatch<float>(const BatchSolveLaunch &, int, hipStream_t);
+template hipError_t launchP2PSolveBatch<double>(const BatchSolveLaunch &, int, hipStream_t);
 
 namespace {
 // A resident finalize kernel (one workgroup; its last three parameters are the sum over the ranks,

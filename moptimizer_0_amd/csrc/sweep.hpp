@@ -1,5 +1,5 @@
 // Internal interface between the host units of the library (sweep_launch.cpp, resident.cpp, cost.cpp,
-// icp.cpp, lm.cpp) and the gfx950 kernels (sweep_kernels.hip, fd_kernels.hip, finalize_kernels.hip,
+// icp.cpp, lm.cpp, batch.cpp) and the gfx950 kernels (sweep_kernels.hip, fd_kernels.hip, finalize_kernels.hip,
 // icp_match.hip, layout_kernels.hip).
 #pragma once
 
@@ -328,6 +328,31 @@ hipError_t launchP2PSolveSmall(const S *tiles, int num_tiles, const P2PSweepArgs
                                const AffineBasis *d_basis, double *result, const LmProblem &problem,
                                const S *x0, int max_points, int fd_cov, hipStream_t stream);
 
+// B such minimisations in one launch of B workgroups, one problem per workgroup (mopt_batch, batch.cpp;
+// finalize_kernels.hip p2pSolveBatchKernel).  Everything per problem is an array indexed by the problem:
+// problem i sweeps tiles [first_tile[i], first_tile[i + 1]) of `tiles` (at most solveSmallMaxTiles()),
+// whose slots are numbered from 0 within the problem (args[i].count masks the padding); `problem` is the
+// one description the batch shares (options, Jacobian mode, fd_per_iterate) — its pointers and
+// fd_source_bound are filled in per workgroup on the device.
+constexpr int kBatchResultStride = 48;  // doubles per problem's H | b | sum_sq (43), to whole 128-byte lines
+struct BatchSolveLaunch {
+  const void *tiles = nullptr;
+  const int *first_tile = nullptr;        // device, [B + 1]
+  const LmProblem *problem = nullptr;     // device
+  void *args = nullptr;                   // device, P2PSweepArgs<S>[B]
+  AffineBasis *basis = nullptr;           // device, [B]
+  double *results = nullptr;              // device, [B][kBatchResultStride]
+  LmControl *controls = nullptr;          // device, [B][kLmControlBlocks]
+  LmReport *reports = nullptr;            // mapped host memory as the device addresses it, [B]
+  const void *starts = nullptr;           // device, S[B][kMaxWideParams]: the start poses, zero-padded
+  const double *source_bounds = nullptr;  // device, [B]
+  int num_problems = 0;
+  int max_points = 0;
+  int fd_per_iterate = 0;                 // as problem->fd_per_iterate (host copy: names the kernel)
+};
+template <typename S>
+hipError_t launchP2PSolveBatch(const BatchSolveLaunch &launch, int fd_cov, hipStream_t stream);
+
 // Resident forms: per-x constants read from HBM (`d_args`, `d_basis`), early exit on control->done,
 // peer-combine sequence = peers.sequence + control->trial.
 template <typename S>
@@ -388,6 +413,17 @@ hipError_t launchRelayoutP2P(const S *src_xyz, const S *tgt_xyz, long long count
 hipError_t launchRelayoutReproj(const double *points_xyzw, const int32_t *pixels_uv,
                                 long long count, unsigned char *tiles, int num_tiles,
                                 hipStream_t stream);
+// The same for a batch of problems behind one another in the caller's arrays (mopt_batch): problem i owns
+// correspondences [offsets[i], offsets[i + 1]) and tiles [first_tile[i], first_tile[i + 1]), each problem
+// padded to whole tiles of its own; one launch over all tiles.  offsets / first_tile: device memory.
+template <typename S>
+hipError_t launchRelayoutP2PBatch(const S *src_xyz, const S *tgt_xyz, const long long *offsets,
+                                  const int *first_tile, int num_problems, int total_tiles, S *tiles,
+                                  hipStream_t stream);
+// ... and the sources' bounding box per problem: boxes[6 i ..] = minima | maxima of problem i, as doubles
+template <typename S>
+hipError_t launchSourceBoxBatch(const S *tiles, const long long *offsets, const int *first_tile,
+                                int num_problems, double *boxes, hipStream_t stream);
 // Bounding box of the sources of laid-out tiles: box[0..2] the minima, box[3..5] the maxima, as
 // sourceBoxKey()s (six 64-bit words of device memory, initialised here).  decodeSourceBox() on the host.
 template <typename S>

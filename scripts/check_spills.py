@@ -49,12 +49,16 @@ ACCEPTED_SGPR_SPILLS = (
     ("mopt::p2pSolveSmallKernel<double, 0>", 170, "LM step + two sweep forms inside a loop"),
     ("mopt::p2pSolveSmallKernel<double, 1>", 170, "LM step + two sweep forms inside a loop"),
     ("mopt::p2pSolveSmallKernel<double, 2>", 216, "LM step + two sweep forms inside a loop"),
+    # the same body with a workgroup index (a batch of small problems, one per workgroup): it has 88 bytes of kernel
+    # arguments where the kernel above has 1.4 KB of them, and parks 32-46 scalars in every variant
+    ("mopt::p2pSolveBatchKernel<", 56, "the body of p2pSolveSmallKernel"),
 )
 # Vector registers the allocator moved to the accumulation registers of the same lane (vgpr spills
 # with NO scratch memory): for the kernel that holds its correspondences in registers across a whole
 # minimisation that is where idle values belong.
 ACCEPTED_AGPR_RESIDENT = (
     ("mopt::p2pSolveSmallKernel<", 32),  # (0 since n is fixed at compile time; 20-28 before)
+    ("mopt::p2pSolveBatchKernel<", 32),  # (the same body; 0)
 )
 FIELDS = ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "private_segment_fixed_size")
 
