@@ -199,6 +199,52 @@ MOPT_API int mopt_icp_get_matches(mopt_cost *cost, void *tgt_out_xyz);
 MOPT_API int mopt_icp_grid(const mopt_cost *cost, double *cell_edge, int *reach, int dims[3],
                            double origin[3]);
 
+/* ---- Voxel-grid downsampling of a point cloud on the GPU -------------------------------------
+ * What a registration pipeline runs on a raw scan before it builds a cost (PCL's VoxelGrid, Open3D's
+ * voxel_down_sample); the reference has no counterpart — model.h:24-26 leaves correspondences and
+ * everything before them to the user.  `count` packed xyz triples in, one point per occupied voxel of
+ * edge `leaf` out.  Semantics, all arithmetic in fp64 (an fp32 cloud is widened first):
+ *  - a point with a NaN or infinite coordinate is dropped: it is in no voxel and does not shape the
+ *    bounding box (as in the ICP calls, |v| > 1e300 counts as infinite);
+ *  - the lattice is anchored at the world origin, so two clouds thinned with one `leaf` share their
+ *    voxels.  With lo / hi the bounding box of the finite points, per axis a:
+ *      origin_a = floor(lo_a / leaf) * leaf,   dims_a = (int)floor((hi_a - origin_a) / leaf) + 1,
+ *      cell_a = clamp(floor((v_a - origin_a) / leaf), 0, dims_a - 1),
+ *      id = cell_x + dims_x * (cell_y + dims_y * cell_z)       (the cell rule of mopt_icp_grid);
+ *  - output row k belongs to the k-th occupied voxel in ascending id: out_xyz its points' arithmetic
+ *    mean (summed in fp64, divided, rounded once to the scalar type), out_counts[k] its population;
+ *  - *out_count is always the number of occupied voxels.  When it exceeds `capacity`, or out_xyz is
+ *    NULL, nothing is written to out_xyz or out_counts and the call still returns MOPT_OK: call once
+ *    for the count, then again with buffers of that size;
+ *  - two calls on the same input give the same bits: the sums are taken in an order fixed by the
+ *    points' positions in the caller's array, without floating-point atomics;
+ *  - count == 0 or no finite point: *out_count = 0, MOPT_OK.
+ * MOPT_CLOUD_INPUT_DEVICE takes xyz from device memory on `device` (complete when the call is made:
+ * synchronise the stream that produced it, as for mopt_icp_create_from; it is read in place, not
+ * copied); MOPT_CLOUD_OUTPUT_DEVICE writes out_xyz and out_counts there, ready for
+ * mopt_icp_create_from(..., MOPT_INPUT_DEVICE).  out_count is host memory either way.  The call
+ * blocks and works on a pooled stream of the library's own.
+ * MOPT_ERR_INVALID_ARGUMENT, before any device is looked for: out_count NULL, scalar_bytes not 4 or
+ * 8, unknown flags bits, count < 0 or >= 2^31, leaf not finite or <= 0, xyz NULL with count > 0.  And
+ * once the bounding box is known: dims_x * dims_y * dims_z > 2^31 - 1 (the sort's keys are 32 bits;
+ * PCL refuses the same case, "leaf size too small for the input dataset") — the message names the
+ * extent and the smallest leaf that fits. */
+enum mopt_cloud_flags {
+  MOPT_CLOUD_INPUT_DEVICE = 1, /* xyz is device memory on `device`                          */
+  MOPT_CLOUD_OUTPUT_DEVICE = 2 /* out_xyz / out_counts are device memory on `device`        */
+};
+MOPT_API int mopt_cloud_voxel_downsample(int device, int scalar_bytes, const void *xyz, int64_t count,
+                                         double leaf, unsigned flags /* mopt_cloud_flags */,
+                                         void *out_xyz /* capacity * 3 scalars, may be NULL */,
+                                         int32_t *out_counts /* capacity entries, may be NULL */,
+                                         int64_t capacity, int64_t *out_count /* required */);
+/* For measurements: device time of the stages of the calling thread's last
+ * mopt_cloud_voxel_downsample, from events on its stream, in milliseconds — stage-in copy, bounding
+ * box, keys and sort, head flags and scan, centroids, copy-out — into stage_ms (may be NULL); then
+ * switches the recording on or off for that thread's next calls (off by default: no events). */
+#define MOPT_CLOUD_VOXEL_STAGES 6
+MOPT_API int mopt_cloud_voxel_profile(int enabled, double *stage_ms /* MOPT_CLOUD_VOXEL_STAGES */);
+
 /* Reprojection (camera-calibration) cost, fp64, numeric Jacobian only.  points_xyzw: packed
  * 4-vectors (32 B); pixels_uv: packed int32 pairs (8 B).  camera_3x4 / frame_4x4: row-major
  * constants (tst/camera_calibration.cpp:22-30); NULL selects the reference's values. */

@@ -30,5 +30,6 @@ from ._capi import (  # noqa: F401
     Point2PointGroup,
     ReprojectionCost,
     ScalarModelCost,
+    voxel_downsample,
 )
 from .sharded import ShardedSweep, shard_range  # noqa: F401

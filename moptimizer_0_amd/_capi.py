@@ -17,6 +17,8 @@ MOPT_OK = 0
 JAC_ANALYTIC, JAC_ANALYTIC_TST_LAYOUT, JAC_NUMERIC, JAC_ANALYTIC_LEFT, JAC_ANALYTIC_RIGHT = 0, 1, 2, 3, 4
 LOSS_NONE, LOSS_GEMAN_MCCLURE = 0, 1
 INPUT_HOST, INPUT_DEVICE = 0, 1
+CLOUD_INPUT_DEVICE, CLOUD_OUTPUT_DEVICE = 1, 2
+CLOUD_VOXEL_STAGES = ("stage_in", "bounding_box", "sort", "flags_scan", "centroids", "copy_out")
 KERNEL_AUTO, KERNEL_LITERAL, KERNEL_MOMENTS, KERNEL_MOMENTS_ALWAYS = 0, 1, 2, 3
 COMBINE_NONE, COMBINE_RCCL, COMBINE_HOST, COMBINE_PEER = 0, 1, 2, 3
 COMBINE_NAMES = {COMBINE_NONE: "none", COMBINE_RCCL: "rccl", COMBINE_HOST: "host", COMBINE_PEER: "peer"}
@@ -79,6 +81,10 @@ def load():
         "mopt_icp_grid": [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                           ctypes.POINTER(ctypes.c_double)],
+        "mopt_cloud_voxel_downsample": [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_double, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
+                                        ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
+        "mopt_cloud_voxel_profile": [ctypes.c_int, ctypes.POINTER(ctypes.c_double)],
         "mopt_reprojection_create": [c_void_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_uint],
@@ -228,6 +234,51 @@ def se3_plus_right(x, delta, dtype=np.float64):
     out = np.zeros(6, dtype=dtype)
     check(load().mopt_se3_plus_right(x.itemsize, _ptr(x), _ptr(delta), _ptr(out)))
     return out
+
+
+def voxel_downsample(xyz, leaf, device=0, return_counts=False):
+    """mopt_cloud_voxel_downsample: one centroid per occupied voxel of edge `leaf`, in ascending voxel
+    id.  A numpy array (n, 3) of float32 / float64 goes in from the host and comes back as numpy; a
+    contiguous torch tensor on a HIP device is read in place and the result is a torch tensor on that
+    device (its stream is synchronised first).  Two calls: the count, then the points."""
+    lib = load()
+    n_out = ctypes.c_int64(0)
+    if hasattr(xyz, "data_ptr"):
+        import torch
+        assert xyz.is_cuda and xyz.is_contiguous()
+        if xyz.dtype not in (torch.float32, torch.float64):
+            raise TypeError("voxel_downsample takes float32 or float64 clouds, not %s" % xyz.dtype)
+        torch.cuda.synchronize(xyz.device)
+        dev, size, n = xyz.device.index or 0, xyz.element_size(), xyz.numel() // 3
+        flags = CLOUD_INPUT_DEVICE | CLOUD_OUTPUT_DEVICE
+        src = ctypes.c_void_p(xyz.data_ptr())
+        check(lib.mopt_cloud_voxel_downsample(dev, size, src, n, float(leaf), flags, None, None, 0,
+                                              ctypes.byref(n_out)))
+        k = n_out.value
+        out = torch.empty((k, 3), dtype=xyz.dtype, device=xyz.device)
+        counts = torch.empty((k,), dtype=torch.int32, device=xyz.device)
+        if k > 0:
+            torch.cuda.synchronize(xyz.device)
+            check(lib.mopt_cloud_voxel_downsample(dev, size, src, n, float(leaf), flags,
+                                                  ctypes.c_void_p(out.data_ptr()),
+                                                  ctypes.c_void_p(counts.data_ptr()), k,
+                                                  ctypes.byref(n_out)))
+            assert n_out.value == k
+        return (out, counts) if return_counts else out
+    xyz = np.asarray(xyz)
+    dt = xyz.dtype if xyz.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+    xyz = np.ascontiguousarray(xyz, dtype=dt).reshape(-1, 3)
+    n = xyz.shape[0]
+    check(lib.mopt_cloud_voxel_downsample(int(device), dt.itemsize, _ptr(xyz), n, float(leaf), 0, None,
+                                          None, 0, ctypes.byref(n_out)))
+    k = n_out.value
+    out = np.zeros((k, 3), dtype=dt)
+    counts = np.zeros(k, dtype=np.int32)
+    if k > 0:
+        check(lib.mopt_cloud_voxel_downsample(int(device), dt.itemsize, _ptr(xyz), n, float(leaf), 0,
+                                              _ptr(out), _ptr(counts), k, ctypes.byref(n_out)))
+        assert n_out.value == k
+    return (out, counts) if return_counts else out
 
 
 def link_costs(costs):

@@ -27,16 +27,23 @@ namespace {
 
 constexpr int kBoxBlocks = 512;
 
-template <typename S>
+// WHOLE_POINTS: a point with any NaN or infinite coordinate shapes no axis (the voxel filter's rule;
+// the search's grid takes every finite coordinate)
+template <typename S, bool WHOLE_POINTS>
 __global__ __launch_bounds__(kBlockThreads) void boundingBoxKernel(const S *xyz, long long m,
                                                                    double *block_lohi) {
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
   for (long long i = (long long)blockIdx.x * kBlockThreads + threadIdx.x; i < m;
        i += (long long)gridDim.x * kBlockThreads) {
+    bool whole = true;
+    if (WHOLE_POINTS) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) whole = whole && fabs(double(xyz[3 * i + a])) <= 1e300;
+    }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       const double v = double(xyz[3 * i + a]);
-      const bool finite = fabs(v) <= 1e300;  // (NaN and +-Inf coordinates do not shape the grid)
+      const bool finite = whole && fabs(v) <= 1e300;  // (NaN and +-Inf coordinates do not shape the grid)
       lo[a] = finite && v < lo[a] ? v : lo[a];
       hi[a] = finite && v > hi[a] ? v : hi[a];
     }
@@ -275,15 +282,19 @@ inline int blocksFor(long long m) { return int((m + kBlockThreads - 1) / kBlockT
 
 template <typename S>
 hipError_t icpBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3],
-                          hipStream_t stream) {
+                          hipStream_t stream, bool whole_points) {
   for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0;
   if (m <= 0) return hipSuccess;
   const int grid = blocksFor(m) < kBoxBlocks ? blocksFor(m) : kBoxBlocks;
   double *d_part = nullptr;
   hipError_t e = mopt_detail::deviceAlloc(reinterpret_cast<void **>(&d_part), size_t(grid) * 6 * sizeof(double));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(boundingBoxKernel<S>, dim3(grid), dim3(kBlockThreads), 0, stream, d_xyz, m,
-                     d_part);
+  if (whole_points)
+    hipLaunchKernelGGL((boundingBoxKernel<S, true>), dim3(grid), dim3(kBlockThreads), 0, stream, d_xyz,
+                       m, d_part);
+  else
+    hipLaunchKernelGGL((boundingBoxKernel<S, false>), dim3(grid), dim3(kBlockThreads), 0, stream, d_xyz,
+                       m, d_part);
   std::vector<double> part(size_t(grid) * 6);
   e = hipGetLastError();
   if (e == hipSuccess)
@@ -310,7 +321,7 @@ hipError_t icpBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3
 template <typename S>
 hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], double cell,
                          const int dims[3], int *d_perm, int *d_cell_start, hipStream_t stream,
-                         long long *num_parked) {
+                         long long *num_parked, unsigned int *d_sorted_keys) {
   if (num_parked) *num_parked = 0;
   long long ncells = 1;
   GridShape g;
@@ -380,6 +391,9 @@ hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], do
   }
   const unsigned int *keys_sorted = keys_in;
   e = hipGetLastError();
+  if (e == hipSuccess && d_sorted_keys)
+    e = hipMemcpyAsync(d_sorted_keys, keys_sorted, size_t(m) * sizeof(unsigned int),
+                       hipMemcpyDeviceToDevice, stream);
   if (e == hipSuccess && d_cell_start) {
     hipLaunchKernelGGL(cellStartKernel, dim3(blocksFor(ncells + 1)), dim3(kBlockThreads), 0, stream,
                        keys_sorted, m, int(ncells), d_cell_start);
@@ -411,6 +425,25 @@ hipError_t icpGatherPoints(const S *d_xyz, const int *d_perm, long long m, S *d_
     hipLaunchKernelGGL((gatherPointsKernel<S, 3>), dim3(blocksFor(m)), dim3(kBlockThreads), 0,
                        stream, d_xyz, d_perm, m, d_out);
   return hipGetLastError();
+}
+
+// the three scan kernels above over a caller's table (cloud_voxel.hip: the voxel filter's head flags)
+hipError_t icpExclusiveScan(unsigned int *d_data, long long length, hipStream_t stream) {
+  if (length <= 0) return hipSuccess;
+  const int scan_tiles = int((length + kScanTile - 1) / kScanTile);
+  unsigned int *tile_totals = nullptr;
+  hipError_t e = mopt_detail::deviceAlloc(reinterpret_cast<void **>(&tile_totals), size_t(scan_tiles) * sizeof(unsigned int));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(scanTilesKernel, dim3(scan_tiles), dim3(kBlockThreads), 0, stream, d_data, length,
+                     tile_totals);
+  hipLaunchKernelGGL(scanTotalsKernel, dim3(1), dim3(kBlockThreads), 0, stream, tile_totals, scan_tiles);
+  hipLaunchKernelGGL(addTileOffsetsKernel, dim3(scan_tiles), dim3(kBlockThreads), 0, stream, d_data,
+                     length, tile_totals);
+  e = hipGetLastError();
+  const hipError_t synced = hipStreamSynchronize(stream);  // the totals go back to the pool here
+  if (e == hipSuccess) e = synced;
+  mopt_detail::deviceRelease(tile_totals);
+  return e;
 }
 
 // how many cells hold at least one target: one count per workgroup, added up on the host (this is
@@ -448,9 +481,11 @@ hipError_t icpCountOccupiedCells(const int *d_cell_start, long long ncells, long
 }
 
 #define MOPT_INSTANTIATE_GRID(S)                                                                  \
-  template hipError_t icpBoundingBox<S>(const S *, long long, double[3], double[3], hipStream_t); \
+  template hipError_t icpBoundingBox<S>(const S *, long long, double[3], double[3], hipStream_t,  \
+                                        bool);                                                    \
   template hipError_t icpSortByCell<S>(const S *, long long, const double[3], double,             \
-                                       const int[3], int *, int *, hipStream_t, long long *);     \
+                                       const int[3], int *, int *, hipStream_t, long long *,      \
+                                       unsigned int *);                                           \
   template hipError_t icpGatherPoints<S>(const S *, const int *, long long, S *, bool, hipStream_t);
 MOPT_INSTANTIATE_GRID(double)
 MOPT_INSTANTIATE_GRID(float)
