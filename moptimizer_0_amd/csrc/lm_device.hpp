@@ -138,7 +138,9 @@ __device__ __forceinline__ S forwardStep(S xj) {
 
 // delta = (H + lambda diag H)^{-1} (-b) by LDL^T with diagonal pivoting: the factorisation the
 // reference asks Eigen for (levenberg_marquadt_dyn.cpp:78-80), operation for operation the host
-// statement of tests/support/moptimizer_caller/ldlt.hpp (vanishing pivots give a zero component).
+// statement of tests/support/moptimizer_caller/ldlt.hpp (vanishing pivots give a zero component;
+// tests/test_gpu_device_units.py holds the two to the same bits, and every function of this header
+// down to solveDampedPositive to a long-double reference, through tests/cpp/device_units.hip).
 // Runs on one lane; its work arrays live in LDS (indexed dynamically: as private arrays they would
 // go to scratch memory, a global-memory round trip per dependent access).
 template <typename S, int NMAX>
@@ -213,104 +215,6 @@ __device__ void solveDamped(const S *H, const S *b, S lambda, int n, SolveScratc
   for (int i = 0; i < n; ++i) w.delta[perm[i]] = y[i];
 }
 
-// The same factorisation for a compile-time n, fully unrolled so that the matrix lives in registers
-// (every index is a constant after unrolling; the run-time pivot choice becomes a chain of
-// predicated swaps).  One lane runs it: ~n^3 / 3 dependent fp64 operations instead of as many LDS
-// round trips.  Same operations in the same order as solveDamped.
-template <typename S, int N>
-__device__ void solveDampedFixed(const S *H, const S *b, S lambda, S *delta) {
-#pragma clang fp contract(off)
-  S m[N][N];
-  S scaled[N], y[N];
-  int perm[N];
-#pragma unroll
-  for (int c = 0; c < N; ++c)
-#pragma unroll
-    for (int r = 0; r < N; ++r) m[r][c] = H[c * N + r];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    m[i][i] += lambda * H[i * N + i];
-    perm[i] = i;
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    int piv = k;
-    S best = fabs(m[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < N; ++i) {
-      const S v = fabs(m[i][i]);
-      if (v > best) {
-        best = v;
-        piv = i;
-      }
-    }
-#pragma unroll
-    for (int p = k + 1; p < N; ++p) {
-      if (piv == p) {
-#pragma unroll
-        for (int j = 0; j < k; ++j) { const S t = m[k][j]; m[k][j] = m[p][j]; m[p][j] = t; }
-#pragma unroll
-        for (int i = p + 1; i < N; ++i) { const S t = m[i][k]; m[i][k] = m[i][p]; m[i][p] = t; }
-#pragma unroll
-        for (int i = k + 1; i < p; ++i) { const S t = m[i][k]; m[i][k] = m[p][i]; m[p][i] = t; }
-        { const S t = m[k][k]; m[k][k] = m[p][p]; m[p][p] = t; }
-        { const int t = perm[k]; perm[k] = perm[p]; perm[p] = t; }
-      }
-    }
-    S dk = m[k][k];
-#pragma unroll
-    for (int j = 0; j < k; ++j) {
-      scaled[j] = m[k][j] * m[j][j];
-      dk -= m[k][j] * scaled[j];
-    }
-    m[k][k] = dk;
-#pragma unroll
-    for (int i = k + 1; i < N; ++i) {
-      S v = m[i][k];
-#pragma unroll
-      for (int j = 0; j < k; ++j) v -= m[i][j] * scaled[j];
-      m[i][k] = v;
-    }
-    if (fabs(dk) > S(0)) {
-#pragma unroll
-      for (int i = k + 1; i < N; ++i) m[i][k] /= dk;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    S v = S(0);
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-      if (perm[i] == j) v = -b[j];
-    y[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    S v = y[i];
-#pragma unroll
-    for (int j = 0; j < i; ++j) v -= m[i][j] * y[j];
-    y[i] = v;
-  }
-  const S tiny = std::numeric_limits<S>::min();
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    const S d = m[i][i];
-    y[i] = (fabs(d) > tiny) ? y[i] / d : S(0);
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; --i) {
-    S v = y[i];
-#pragma unroll
-    for (int j = i + 1; j < N; ++j) v -= m[j][i] * y[j];
-    y[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i)
-#pragma unroll
-    for (int j = 0; j < N; ++j)
-      if (perm[i] == j) delta[j] = y[i];
-}
-
 // 1 / d to about an ulp: the hardware estimate and two Newton steps (5 instructions; an IEEE fp64
 // division is ~25, and the solve has n of them on its critical path).
 __device__ __forceinline__ double fastReciprocal(double d) {
@@ -328,9 +232,10 @@ __device__ __forceinline__ double fusedMulAdd(double a, double b, double c) { re
 __device__ __forceinline__ float fusedMulAdd(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
 // The same system when H + lambda diag H is safely positive definite — which it is at every step of
-// a well-posed problem: LDL^T in the given order (no pivot search, no predicated row / column
-// exchanges: those are most of the ~800 dependent instructions solveDampedFixed<6> issues on its one
-// lane), multiply-adds fused, reciprocals instead of divisions: ~130 instructions.  A factorisation
+// a well-posed problem: LDL^T in the given order, fully unrolled so that the matrix lives in
+// registers (no pivot search, no row / column exchanges: with a compile-time n those become chains
+// of predicated swaps, most of the ~800 dependent instructions a pivoted register form of n = 6
+// issues on its one lane), multiply-adds fused, reciprocals instead of divisions: ~130 instructions.  A factorisation
 // without pivoting is backward stable for a positive definite matrix, so delta agrees with the
 // pivoted solve to eps * cond(H) — the same pose, not the same bits (no restatement reproduces the
 // reference's Eigen::LDLT bit for bit either).  Returns false, leaving delta untouched, when a pivot
@@ -657,10 +562,10 @@ __device__ __forceinline__ bool lmStepBodyFor(const LmProblem &P, bool init, con
       MOPT_TICK(5);
       // The unpivoted solve in registers where every pivot is clearly positive; where one is not
       // (a singular or indefinite H: the as-written test Jacobian's zero row, a cost with no valid
-      // residual) the pivoted statement of the host runs from LDS — solveDamped, run-time n, the same
-      // operations in the same order as the register form of rounds 2-4 (solveDampedFixed) but cold:
-      // that form's predicated exchanges kept ~80 lane masks alive across the hot path (118 spilled
-      // SGPRs in lmStepKernel<double>, 52 in the fused finalize-and-step kernels).
+      // residual) the pivoted statement of the host runs from LDS — solveDamped, run-time n, cold.
+      // (A pivoted form unrolled into registers was tried in its place: its predicated exchanges
+      // kept ~80 lane masks alive across the hot path — 118 spilled SGPRs in lmStepKernel<double>,
+      // 52 in the fused finalize-and-step kernels; profiles/NOTES.md has the history.)
       bool solved = false;
       if constexpr (kInRegisters) {  // (the 16-wide instantiation never sees these n)
         switch (n) {
