@@ -245,6 +245,44 @@ MOPT_API int mopt_cloud_voxel_downsample(int device, int scalar_bytes, const voi
 #define MOPT_CLOUD_VOXEL_STAGES 6
 MOPT_API int mopt_cloud_voxel_profile(int enabled, double *stage_ms /* MOPT_CLOUD_VOXEL_STAGES */);
 
+/* ---- Surface normals of a point cloud on the GPU ---------------------------------------------
+ * Radius-neighbourhood PCA normals (PCL's NormalEstimation with a search radius, Open3D's
+ * estimate_normals): what a point-to-plane cost needs per target point; the reference has no
+ * counterpart — model.h:24-26 leaves everything in front of the cost to the user.  `count` packed xyz
+ * triples in; row i of every output belongs to input row i, in the caller's order.  Semantics, all
+ * arithmetic in fp64 (an fp32 cloud is widened first, results are rounded once to the scalar type):
+ *  - a point with a NaN or infinite coordinate (as in the ICP and voxel calls, |v| > 1e300 counts as
+ *    infinite) is nobody's neighbour; its own row is a NaN normal, a NaN curvature and count 0;
+ *  - the neighbourhood of p is every finite point q of the same cloud, p itself included, with
+ *      d = q - p per axis,   d2 = (dx*dx + dy*dy) + dz*dz <= radius*radius,
+ *    every operation rounded on its own (no fused multiply-add); out_counts[i] is its size k;
+ *  - k < max(min_neighbors, 3): the normal and the curvature are NaN, the count is still written;
+ *  - moments about the query point: s = sum d, M = sum d d^T, mu = s / k, C = M / k - mu mu^T (every
+ *    |d| <= radius, so nothing cancels at map-frame coordinates);
+ *  - the normal is the unit eigenvector of C for its smallest eigenvalue l0 <= l1 <= l2 (cyclic Jacobi
+ *    in fp64), with the sign for which n . (viewpoint - p) >= 0; curvature = l0 / (l0 + l1 + l2), PCL's
+ *    surface variation, or 0 when the trace is 0.  Where l1 - l0 is not resolved by fp64 (an isotropic
+ *    neighbourhood, points on a line) the row is still some unit vector: its direction is unspecified;
+ *  - two calls on the same input give the same bits: the points are binned into a lattice of cells of
+ *    edge >= radius (the voxel call's lattice rule), and every sum runs over the 3 x 3 x 3 cells around
+ *    the point's own in ascending (z, y, x) cell offset and, within a cell, in ascending index in the
+ *    caller's array (the sort is stable).  No floating-point atomics.
+ * MOPT_CLOUD_INPUT_DEVICE takes xyz from device memory on `device` (complete when the call is made; it
+ * is read in place); with MOPT_CLOUD_OUTPUT_DEVICE out_normals, out_curvature and out_counts are all
+ * device memory there.  `viewpoint` is host memory either way.  The call blocks and works on a pooled
+ * stream of the library's own.
+ * MOPT_ERR_INVALID_ARGUMENT, before any device is looked for: out_normals NULL with count > 0,
+ * scalar_bytes not 4 or 8, unknown flags bits, count < 0 or >= 2^31, radius not finite or <= 0,
+ * min_neighbors < 0, xyz NULL with count > 0, a non-finite viewpoint.  count == 0: MOPT_OK, nothing is
+ * written. */
+MOPT_API int mopt_cloud_estimate_normals(int device, int scalar_bytes, const void *xyz, int64_t count,
+                                         double radius, int min_neighbors,
+                                         const double *viewpoint /* 3, host; NULL = (0,0,0) */,
+                                         unsigned flags /* mopt_cloud_flags */,
+                                         void *out_normals   /* count * 3 scalars, required */,
+                                         void *out_curvature /* count scalars, may be NULL */,
+                                         int32_t *out_counts /* count entries, may be NULL */);
+
 /* Reprojection (camera-calibration) cost, fp64, numeric Jacobian only.  points_xyzw: packed
  * 4-vectors (32 B); pixels_uv: packed int32 pairs (8 B).  camera_3x4 / frame_4x4: row-major
  * constants (tst/camera_calibration.cpp:22-30); NULL selects the reference's values. */

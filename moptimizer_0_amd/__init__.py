@@ -30,6 +30,7 @@ from ._capi import (  # noqa: F401
     Point2PointGroup,
     ReprojectionCost,
     ScalarModelCost,
+    estimate_normals,
     voxel_downsample,
 )
 from .sharded import ShardedSweep, shard_range  # noqa: F401

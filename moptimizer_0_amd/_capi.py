@@ -85,6 +85,9 @@ def load():
                                         ctypes.c_double, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)],
         "mopt_cloud_voxel_profile": [ctypes.c_int, ctypes.POINTER(ctypes.c_double)],
+        "mopt_cloud_estimate_normals": [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                        ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p],
         "mopt_reprojection_create": [c_void_pp, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_uint],
@@ -279,6 +282,51 @@ def voxel_downsample(xyz, leaf, device=0, return_counts=False):
                                               _ptr(out), _ptr(counts), k, ctypes.byref(n_out)))
         assert n_out.value == k
     return (out, counts) if return_counts else out
+
+
+def estimate_normals(xyz, radius, min_neighbors=3, viewpoint=None, device=0, return_curvature=False,
+                     return_counts=False):
+    """mopt_cloud_estimate_normals: one unit normal per point from the PCA of its radius neighbourhood,
+    turned towards `viewpoint` (default: the origin); NaN rows where fewer than max(min_neighbors, 3)
+    neighbours lie within `radius` or the point is not finite.  A numpy array (n, 3) of float32 / float64
+    goes in from the host and comes back as numpy; a contiguous torch tensor on a HIP device is read in
+    place and the results are torch tensors on that device (its stream is synchronised first).  Returns
+    the normals, then the curvature and the neighbour counts (int32) where asked for."""
+    lib = load()
+    view = None
+    if viewpoint is not None:
+        view = (ctypes.c_double * 3)(*[float(v) for v in np.asarray(viewpoint, dtype=np.float64).reshape(3)])
+    if hasattr(xyz, "data_ptr"):
+        import torch
+        assert xyz.is_cuda and xyz.is_contiguous()
+        if xyz.dtype not in (torch.float32, torch.float64):
+            raise TypeError("estimate_normals takes float32 or float64 clouds, not %s" % xyz.dtype)
+        torch.cuda.synchronize(xyz.device)
+        dev, n = xyz.device.index or 0, xyz.numel() // 3
+        normals = torch.empty((n, 3), dtype=xyz.dtype, device=xyz.device)
+        curvature = torch.empty((n,), dtype=xyz.dtype, device=xyz.device) if return_curvature else None
+        counts = torch.empty((n,), dtype=torch.int32, device=xyz.device) if return_counts else None
+        torch.cuda.synchronize(xyz.device)
+
+        def ptr(t):
+            return None if t is None else ctypes.c_void_p(t.data_ptr())
+        check(lib.mopt_cloud_estimate_normals(dev, xyz.element_size(), ptr(xyz), n, float(radius),
+                                              int(min_neighbors), view, CLOUD_INPUT_DEVICE | CLOUD_OUTPUT_DEVICE,
+                                              ptr(normals), ptr(curvature), ptr(counts)))
+    else:
+        xyz = np.asarray(xyz)
+        dt = xyz.dtype if xyz.dtype in (np.float32, np.float64) else np.dtype(np.float64)
+        xyz = np.ascontiguousarray(xyz, dtype=dt).reshape(-1, 3)
+        n = xyz.shape[0]
+        normals = np.zeros((n, 3), dtype=dt)
+        curvature = np.zeros(n, dtype=dt) if return_curvature else None
+        counts = np.zeros(n, dtype=np.int32) if return_counts else None
+        check(lib.mopt_cloud_estimate_normals(int(device), dt.itemsize, _ptr(xyz), n, float(radius),
+                                              int(min_neighbors), view, 0, _ptr(normals),
+                                              None if curvature is None else _ptr(curvature),
+                                              None if counts is None else _ptr(counts)))
+    extra = [out for out, asked in ((curvature, return_curvature), (counts, return_counts)) if asked]
+    return (normals, *extra) if extra else normals
 
 
 def link_costs(costs):

@@ -1,6 +1,6 @@
 // Internal interface between the host units of the library (sweep_launch.cpp, resident.cpp, cost.cpp,
 // icp.cpp, lm.cpp, batch.cpp) and the gfx950 kernels (sweep_kernels.hip, fd_kernels.hip, finalize_kernels.hip,
-// icp_match.hip, layout_kernels.hip, icp_grid.hip, cloud_voxel.hip).
+// icp_match.hip, layout_kernels.hip, icp_grid.hip, cloud_voxel.hip, cloud_normals.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -548,6 +548,18 @@ template <typename S>
 hipError_t launchVoxelCentroids(const S *d_xyz, const int *d_perm, const unsigned int *d_sorted_keys,
                                 const unsigned int *d_voxels_before, long long kept, S *d_out_xyz,
                                 int32_t *d_out_counts, void *d_carry, hipStream_t stream);
+
+// Radius-neighbourhood PCA normals (cloud_normals.hip; cloud.cpp is its host side).  All
+// pointers are device memory.  The cloud arrives sorted by icpSortByCell over a lattice whose cell edge
+// is >= radius: d_perm and d_sorted_keys (`count` entries, the `kept` points with finite coordinates
+// first), d_cell_start (cells + 1 offsets into that order) and d_cell_xyz, the first `kept` points
+// gathered in that order, padded to 4 scalars.  Rows d_perm[k] of the outputs are written for every
+// k < count (NaN and 0 from `kept` on); d_curvature and d_counts may be NULL.
+template <typename S>
+hipError_t launchCloudNormals(const S *d_cell_xyz, const int *d_perm, const unsigned int *d_sorted_keys,
+                              const int *d_cell_start, long long count, long long kept, const int dims[3],
+                              double radius, int min_neighbors, const double viewpoint[3], S *d_normals,
+                              S *d_curvature, int32_t *d_counts, hipStream_t stream);
 
 // sum of the search's per-wave matched counts -> mapped host memory (as one double) + flag
 hipError_t launchPublishCounter(const unsigned int *d_wave_counts, long long num_waves,
