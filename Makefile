@@ -17,7 +17,8 @@ LIB         = $(LIBDIR)/libmoptimizer_hip.so
 
 PUBLIC_HEADERS = include/moptimizer_hip.h include/moptimizer_amd/so3.hpp $(CSRC)/sweep.hpp $(CSRC)/fd_device.hpp \
                  $(CSRC)/sweep_device.hpp $(CSRC)/jit_model.hpp $(CSRC)/cost_state.hpp $(CSRC)/lm_device.hpp $(CSRC)/aql.hpp \
-                 $(CSRC)/dispatch.hpp $(CSRC)/sweep_choice.hpp $(CSRC)/publish_device.hpp $(CSRC)/normals_device.hpp
+                 $(CSRC)/dispatch.hpp $(CSRC)/sweep_choice.hpp $(CSRC)/publish_device.hpp $(CSRC)/normals_device.hpp \
+                 $(CSRC)/cell_order.hpp $(CSRC)/cell_lattice.hpp
 
 all: $(LIB)
 
@@ -25,12 +26,12 @@ $(OBJDIR) $(LIBDIR):
 	mkdir -p $@
 
 # One code object per device unit; the host units are compiled as HIP too.
-DEVICE_UNITS = sweep_kernels finalize_kernels icp_match layout_kernels fd_kernels icp_grid lm_kernels cloud_voxel cloud_normals
+DEVICE_UNITS = sweep_kernels finalize_kernels icp_match layout_kernels fd_kernels cell_order lm_kernels cloud_voxel cloud_normals
 HOST_UNITS   = c_abi cost sweep_launch blocking resident icp group aql jit_model device_pool combine lm batch cloud
 OBJS         = $(DEVICE_UNITS:%=$(OBJDIR)/%.o) $(HOST_UNITS:%=$(OBJDIR)/%.o)
 
 # leading scalar kernel arguments preloaded into SGPRs at wave launch (gfx940+): the sweeps and what
-# shares their argument conventions; icp_grid, lm_kernels, cloud_voxel and cloud_normals are built without it
+# shares their argument conventions; cell_order, lm_kernels, cloud_voxel and cloud_normals are built without it
 PRELOAD = -mllvm -amdgpu-kernarg-preload-count=4
 $(OBJDIR)/sweep_kernels.o $(OBJDIR)/finalize_kernels.o $(OBJDIR)/icp_match.o $(OBJDIR)/layout_kernels.o: UNITFLAGS = $(PRELOAD)
 # forward-difference sweeps: without the SLP vectorizer (fd_kernels.hip says why)

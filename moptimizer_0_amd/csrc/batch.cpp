@@ -158,12 +158,8 @@ int mopt_point2point_batch_create(mopt_batch **out, int device, int scalar_bytes
         b->first_tile[i] + int((b->offsets[i + 1] - b->offsets[i] + tile_points - 1) / tile_points);
   b->total_tiles = b->first_tile[B];
 
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(MOPT_ERR_NO_DEVICE, "no HIP device is visible to this process");
-  if (device < 0 || device >= ndev) return fail(MOPT_ERR_INVALID_ARGUMENT, "device index out of range");
+  if (const int rc = selectDevice(device)) return rc;
   b->device = b->config.device = device;
-  MOPT_HIP_TRY(hipSetDevice(device));
   MOPT_HIP_TRY(acquireStream(device, &b->stream));
   hipStream_t s = b->stream;
 

@@ -1,10 +1,10 @@
-// Uniform-grid construction for the correspondence search, on the GPU.
+// Points put in the order of the cells of a uniform lattice, on the GPU (cell_order.hpp): what the
+// correspondence search (icp.cpp), the voxel filter and the normal estimation (cloud.cpp) share.
 //
-// The grid that icpMatchKernel walks (icp_match.hip) is built once per cloud pair:
-//   bounding box of the targets -> cell ids -> stable sort of (cell id, index) -> cell offsets ->
-//   targets gathered cell by cell (32-byte padded), sources gathered in cell order.
-// Everything O(points) runs on the device; the host only picks the grid resolution from the six
-// bounding-box numbers.  The sort is a least-significant-digit radix sort written here for wave64
+//   bounding box of a cloud -> cell ids -> stable sort of (cell id, index) -> cell offsets ->
+//   points gathered in that order (packed, or 32- / 16-byte padded rows)
+// Everything O(points) runs on the device; the host only picks the lattice from the six bounding-box
+// numbers (cell_lattice.hpp).  The sort is a least-significant-digit radix sort written here for wave64
 // (8-bit digits, as many passes as the cell count needs: 2-3 in practice): per pass a per-workgroup
 // digit histogram, an exclusive scan over the (digit, workgroup) table, and a scatter in which
 // every wavefront ranks its 64 keys among equal digits with eight ballots — no atomics on the
@@ -15,12 +15,10 @@
 
 #include <vector>
 
-#include "sweep.hpp"
-
-namespace mopt_detail {  // the size-class cache in front of hipMalloc / hipFree (device_pool.cpp):
-hipError_t deviceAlloc(void **out, size_t bytes);  // a grid is built per cloud pair, and hipFree
-void deviceRelease(void *p);                       // synchronises the device every time
-}  // namespace mopt_detail
+#include "cell_order.hpp"
+// deviceAlloc / deviceRelease, the size-class cache in front of hipMalloc / hipFree (device_pool.cpp): an
+// order is built per cloud, and hipFree synchronises the device every time
+#include "cost_state.hpp"
 
 namespace mopt {
 namespace {
@@ -76,17 +74,11 @@ __global__ __launch_bounds__(kBlockThreads) void boundingBoxKernel(const S *xyz,
   }
 }
 
-struct GridShape {
-  double origin[3];
-  double cell;
-  int dims[3];
-};
-
 // cell id of every point (clamped into the grid); with parked_key >= 0 a point with a NaN or
 // infinite coordinate gets that key instead — one past the last cell, so it sorts behind all others
 template <typename S>
 __global__ __launch_bounds__(kBlockThreads) void cellKeyKernel(const S *xyz, long long m,
-                                                               const GridShape g,
+                                                               const CellLattice g,
                                                                long long parked_key,
                                                                unsigned int *keys) {
   const long long i = (long long)blockIdx.x * kBlockThreads + threadIdx.x;
@@ -97,7 +89,7 @@ __global__ __launch_bounds__(kBlockThreads) void cellKeyKernel(const S *xyz, lon
   for (int a = 0; a < 3; ++a) {
     const double v = double(xyz[3 * i + a]);
     finite = finite && fabs(v) <= 1e300;
-    double c = floor((v - g.origin[a]) / g.cell);
+    double c = floor((v - g.origin[a]) / g.edge);
     c = c >= 0.0 ? c : 0.0;  // (also a NaN coordinate: such a point is never anyone's nearest)
     c = c >= double(g.dims[a]) ? double(g.dims[a] - 1) : c;
     id += (long long)c * stride;
@@ -281,8 +273,8 @@ inline int blocksFor(long long m) { return int((m + kBlockThreads - 1) / kBlockT
 }  // namespace
 
 template <typename S>
-hipError_t icpBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3],
-                          hipStream_t stream, bool whole_points) {
+hipError_t cloudBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3],
+                            hipStream_t stream, bool whole_points) {
   for (int a = 0; a < 3; ++a) lo[a] = hi[a] = 0.0;
   if (m <= 0) return hipSuccess;
   const int grid = blocksFor(m) < kBoxBlocks ? blocksFor(m) : kBoxBlocks;
@@ -319,27 +311,19 @@ hipError_t icpBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3
 }
 
 template <typename S>
-hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], double cell,
-                         const int dims[3], int *d_perm, int *d_cell_start, hipStream_t stream,
-                         long long *num_parked, unsigned int *d_sorted_keys) {
-  if (num_parked) *num_parked = 0;
-  long long ncells = 1;
-  GridShape g;
-  for (int a = 0; a < 3; ++a) {
-    g.origin[a] = origin[a];
-    g.dims[a] = dims[a];
-    ncells *= dims[a];
-  }
-  g.cell = cell;
+hipError_t sortByCell(const S *d_xyz, long long m, const CellLattice &g, CellOrder &order,
+                      hipStream_t stream) {
+  order.parked = 0;
+  const long long ncells = g.cells();
   if (m <= 0) {
-    if (d_cell_start)
-      return hipMemsetAsync(d_cell_start, 0, size_t(ncells + 1) * sizeof(int), stream);
+    if (order.d_cell_start)
+      return hipMemsetAsync(order.d_cell_start, 0, size_t(ncells + 1) * sizeof(int), stream);
     return hipSuccess;
   }
-  // scratch: two key buffers, one value buffer (the other one is d_perm) and the histogram table
+  // scratch: two key buffers, one value buffer (the other one is order.d_perm) and the histogram table
   const int num_groups = int((m + kSortTile - 1) / kSortTile);
   int bits = 1;
-  while ((1ll << bits) < ncells + (num_parked ? 1 : 0)) ++bits;
+  while ((1ll << bits) < ncells + (order.park_non_finite ? 1 : 0)) ++bits;  // (the parked key)
   const int passes = (bits + 7) / 8;
   const long long table = (long long)kDigits * num_groups;  // (digit, workgroup) counters
   const int scan_tiles = int((table + kScanTile - 1) / kScanTile);
@@ -367,13 +351,13 @@ hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], do
     return e;
   }
   hipLaunchKernelGGL(cellKeyKernel<S>, dim3(blocksFor(m)), dim3(kBlockThreads), 0, stream, d_xyz, m,
-                     g, num_parked ? ncells : -1ll, keys);
+                     g, order.park_non_finite ? ncells : -1ll, keys);
   const unsigned int *keys_in = keys;
   unsigned int *keys_out = keys_alt;
   const int *values_in = nullptr;  // pass 1: value i = index i
   for (int p = 0; p < passes; ++p) {
-    // ping-pong so that the last pass writes the permutation into d_perm
-    int *values_out = ((passes - 1 - p) % 2 == 0) ? d_perm : values_alt;
+    // ping-pong so that the last pass writes the permutation into order.d_perm
+    int *values_out = ((passes - 1 - p) % 2 == 0) ? order.d_perm : values_alt;
     hipLaunchKernelGGL(radixHistogramKernel, dim3(num_groups), dim3(kBlockThreads), 0, stream,
                        keys_in, m, 8 * p, hist, num_groups);
     hipLaunchKernelGGL(scanTilesKernel, dim3(scan_tiles), dim3(kBlockThreads), 0, stream, hist,
@@ -391,21 +375,21 @@ hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], do
   }
   const unsigned int *keys_sorted = keys_in;
   e = hipGetLastError();
-  if (e == hipSuccess && d_sorted_keys)
-    e = hipMemcpyAsync(d_sorted_keys, keys_sorted, size_t(m) * sizeof(unsigned int),
+  if (e == hipSuccess && order.d_sorted_keys)
+    e = hipMemcpyAsync(order.d_sorted_keys, keys_sorted, size_t(m) * sizeof(unsigned int),
                        hipMemcpyDeviceToDevice, stream);
-  if (e == hipSuccess && d_cell_start) {
+  if (e == hipSuccess && order.d_cell_start) {
     hipLaunchKernelGGL(cellStartKernel, dim3(blocksFor(ncells + 1)), dim3(kBlockThreads), 0, stream,
-                       keys_sorted, m, int(ncells), d_cell_start);
+                       keys_sorted, m, int(ncells), order.d_cell_start);
     e = hipGetLastError();
   }
   long long *d_parked = nullptr;
-  if (e == hipSuccess && num_parked) {
+  if (e == hipSuccess && order.park_non_finite) {
     e = mopt_detail::deviceAlloc(reinterpret_cast<void **>(&d_parked), sizeof(long long));
     if (e == hipSuccess) {
       hipLaunchKernelGGL(countParkedKernel, dim3(1), dim3(1), 0, stream, keys_sorted, m,
                          (unsigned int)ncells, d_parked);
-      e = hipMemcpyAsync(num_parked, d_parked, sizeof(long long), hipMemcpyDeviceToHost, stream);
+      e = hipMemcpyAsync(&order.parked, d_parked, sizeof(long long), hipMemcpyDeviceToHost, stream);
     }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(stream);  // the scratch arrays die here
@@ -415,8 +399,8 @@ hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], do
 }
 
 template <typename S>
-hipError_t icpGatherPoints(const S *d_xyz, const int *d_perm, long long m, S *d_out, bool padded,
-                           hipStream_t stream) {
+hipError_t gatherByOrder(const S *d_xyz, const int *d_perm, long long m, S *d_out, bool padded,
+                         hipStream_t stream) {
   if (m <= 0) return hipSuccess;
   if (padded)
     hipLaunchKernelGGL((gatherPointsKernel<S, 4>), dim3(blocksFor(m)), dim3(kBlockThreads), 0,
@@ -428,7 +412,7 @@ hipError_t icpGatherPoints(const S *d_xyz, const int *d_perm, long long m, S *d_
 }
 
 // the three scan kernels above over a caller's table (cloud_voxel.hip: the voxel filter's head flags)
-hipError_t icpExclusiveScan(unsigned int *d_data, long long length, hipStream_t stream) {
+hipError_t exclusiveScan(unsigned int *d_data, long long length, hipStream_t stream) {
   if (length <= 0) return hipSuccess;
   const int scan_tiles = int((length + kScanTile - 1) / kScanTile);
   unsigned int *tile_totals = nullptr;
@@ -457,8 +441,8 @@ __global__ __launch_bounds__(kBlockThreads) void occupiedCellsKernel(const int *
   if (threadIdx.x == 0) per_block[blockIdx.x] = (unsigned int)in_block;
 }
 
-hipError_t icpCountOccupiedCells(const int *d_cell_start, long long ncells, long long *occupied,
-                                 hipStream_t stream) {
+hipError_t countOccupiedCells(const int *d_cell_start, long long ncells, long long *occupied,
+                              hipStream_t stream) {
   *occupied = 0;
   if (ncells <= 0) return hipSuccess;
   const unsigned blocks = unsigned((ncells + kBlockThreads - 1) / kBlockThreads);
@@ -480,14 +464,13 @@ hipError_t icpCountOccupiedCells(const int *d_cell_start, long long ncells, long
   return hipSuccess;
 }
 
-#define MOPT_INSTANTIATE_GRID(S)                                                                  \
-  template hipError_t icpBoundingBox<S>(const S *, long long, double[3], double[3], hipStream_t,  \
-                                        bool);                                                    \
-  template hipError_t icpSortByCell<S>(const S *, long long, const double[3], double,             \
-                                       const int[3], int *, int *, hipStream_t, long long *,      \
-                                       unsigned int *);                                           \
-  template hipError_t icpGatherPoints<S>(const S *, const int *, long long, S *, bool, hipStream_t);
-MOPT_INSTANTIATE_GRID(double)
-MOPT_INSTANTIATE_GRID(float)
+#define MOPT_INSTANTIATE_ORDER(S)                                                                   \
+  template hipError_t cloudBoundingBox<S>(const S *, long long, double[3], double[3], hipStream_t,  \
+                                          bool);                                                    \
+  template hipError_t sortByCell<S>(const S *, long long, const CellLattice &, CellOrder &,         \
+                                    hipStream_t);                                                   \
+  template hipError_t gatherByOrder<S>(const S *, const int *, long long, S *, bool, hipStream_t);
+MOPT_INSTANTIATE_ORDER(double)
+MOPT_INSTANTIATE_ORDER(float)
 
 }  // namespace mopt

@@ -1,5 +1,5 @@
 // Radius-neighbourhood PCA normals (mopt_cloud_estimate_normals, cloud.cpp): the device half
-// that follows the sort and the gather of icp_grid.hip.  The finite points arrive cell by cell (a lattice
+// that follows the sort and the gather of cell_order.hip.  The finite points arrive cell by cell (a lattice
 // whose cell edge is >= radius, 32- or 16-byte padded rows) with their sorted cell keys and the cells'
 // offsets into that order.
 //   cloudNormalsKernel   one lane per position of the sorted order.  A lane in front of `kept` takes its
@@ -94,13 +94,14 @@ __global__ __launch_bounds__(kBlockThreads) void cloudNormalsKernel(
 
 template <typename S>
 hipError_t launchCloudNormals(const S *d_cell_xyz, const int *d_perm, const unsigned int *d_sorted_keys,
-                              const int *d_cell_start, long long count, long long kept, const int dims[3],
-                              double radius, int min_neighbors, const double viewpoint[3], S *d_normals,
-                              S *d_curvature, int32_t *d_counts, hipStream_t stream) {
+                              const int *d_cell_start, long long count, long long kept,
+                              const CellLattice &lattice, double radius, int min_neighbors,
+                              const double viewpoint[3], S *d_normals, S *d_curvature, int32_t *d_counts,
+                              hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   NormalsArgs g;
   for (int a = 0; a < 3; ++a) {
-    g.dims[a] = dims[a];
+    g.dims[a] = lattice.dims[a];
     g.view[a] = viewpoint[a];
   }
   g.min_k = min_neighbors > 3 ? min_neighbors : 3;
@@ -112,10 +113,10 @@ hipError_t launchCloudNormals(const S *d_cell_xyz, const int *d_perm, const unsi
 }
 
 template hipError_t launchCloudNormals<double>(const double *, const int *, const unsigned int *, const int *,
-                                               long long, long long, const int[3], double, int,
+                                               long long, long long, const CellLattice &, double, int,
                                                const double[3], double *, double *, int32_t *, hipStream_t);
 template hipError_t launchCloudNormals<float>(const float *, const int *, const unsigned int *, const int *,
-                                              long long, long long, const int[3], double, int, const double[3],
-                                              float *, float *, int32_t *, hipStream_t);
+                                              long long, long long, const CellLattice &, double, int,
+                                              const double[3], float *, float *, int32_t *, hipStream_t);
 
 }  // namespace mopt

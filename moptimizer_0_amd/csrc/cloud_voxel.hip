@@ -1,8 +1,8 @@
 // Voxel-grid downsampling (mopt_cloud_voxel_downsample, cloud.cpp): the device half that follows the
-// sort of icp_grid.hip.  The points arrive as a permutation in (voxel id, caller's index) order with
+// sort of cell_order.hip.  The points arrive as a permutation in (voxel id, caller's index) order with
 // their sorted keys; what is done here is the segmented reduction of that order into one centroid per
 // occupied voxel:
-//   voxelHeadFlagsKernel   flag[k] = key[k] != key[k-1]; after the exclusive scan (icpExclusiveScan)
+//   voxelHeadFlagsKernel   flag[k] = key[k] != key[k-1]; after the exclusive scan (exclusiveScan)
 //                          flag[k] is the number of voxels that begin before position k
 //   voxelCentroidKernel    every wave walks 8 x 64 consecutive positions; per 64 a segmented Hillis-
 //                          Steele scan over the lanes (six shuffle steps on x, y, z in fp64 and the count),

@@ -54,14 +54,19 @@ void storeResult(const mopt_cost *c, const double *res, void *hessian, void *b, 
   }
 }
 
-int commonCreate(mopt_cost *c, int device) {
+int selectDevice(int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(MOPT_ERR_NO_DEVICE, "no HIP device is visible to this process");
   if (device < 0 || device >= ndev)
     return fail(MOPT_ERR_INVALID_ARGUMENT, "device index out of range");
-  c->device = device;
   MOPT_HIP_TRY(hipSetDevice(device));
+  return MOPT_OK;
+}
+
+int commonCreate(mopt_cost *c, int device) {
+  if (const int rc = selectDevice(device)) return rc;
+  c->device = device;
   hipDeviceProp_t prop;
   MOPT_HIP_TRY(hipGetDeviceProperties(&prop, device));
   c->num_cus = prop.multiProcessorCount;

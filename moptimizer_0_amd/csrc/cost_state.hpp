@@ -62,7 +62,7 @@ inline int envInt(const char *name, int fallback) {
 
 }  // namespace mopt_detail
 
-// Uniform grid over the target cloud of an ICP cost (built once, on the GPU: icp_grid.hip;
+// Uniform grid over the target cloud of an ICP cost (built once, on the GPU: cell_order.hip;
 // resident in HBM).
 struct IcpMatcher {
   void *d_sorted = nullptr;      // [num_targets][4] scalars grouped by cell
@@ -70,10 +70,8 @@ struct IcpMatcher {
   unsigned int *d_matched = nullptr;  // matched sources per wave of the last counting search
   long long num_waves = 0;
   long long num_sources = 0;  // as handed to mopt_icp_create (the cost holds those with finite coordinates)
-  double origin[3] = {0, 0, 0};
-  double cell = 1.0;
+  mopt::CellLattice lattice;
   int reach = 1;  // cells to the search radius (the search covers (2 reach + 1)^3 cells)
-  int dims[3] = {1, 1, 1};
   double max_dist = 0.0;
   long long num_targets = 0;
   // Sources are stored in grid-cell order (of their un-warped position) so that neighbouring
@@ -273,6 +271,9 @@ void fillIcpArgs(const mopt_cost *c, mopt::IcpMatchArgs<S> &a);
 // left to the runtime's own teardown.)
 hipError_t acquireStream(int device, hipStream_t *out);
 void releaseStream(int device, hipStream_t stream);
+// makes `device` the calling thread's current device: MOPT_OK, or the refusal (no device visible, index
+// out of range) every call that takes a device index gives
+int selectDevice(int device);
 // device, stream, partial / result buffers
 int commonCreate(mopt_cost *c, int device);
 // wait for everything enqueued for this cost, on its own stream and on callers' streams

@@ -1,7 +1,8 @@
 // Correspondence search entry points (mopt_icp_*): the step upstream of the sweep, i.e. what a
 // registration model's update(x) does before every linearization (model.h:24-26,
-// levenberg_marquadt_dyn.cpp:54).  Grid construction and search run on the GPU (icp_grid.hip,
+// levenberg_marquadt_dyn.cpp:54).  Grid construction and search run on the GPU (cell_order.hip,
 // icpMatchKernel in icp_match.hip); this file is their host side.
+#include "cell_order.hpp"
 #include "cost_state.hpp"
 
 #include <cmath>
@@ -13,7 +14,7 @@
 using namespace mopt_detail;
 
 namespace {
-// Grid over the targets and cell-ordered copy of the sources, built on the device (icp_grid.hip);
+// Grid over the targets and cell-ordered copy of the sources, built on the device (cell_order.hip);
 // the host only chooses the resolution.  On return `d_src_sorted` holds the n sources in cell
 // order (packed xyz) and matcher->d_order (device memory) the original index of each.
 template <typename S>
@@ -32,84 +33,48 @@ int buildIcpGrid(const S *src, long long n, const S *tgt, long long m, double ma
   if (m > 0) MOPT_HIP_TRY(hipMemcpyAsync(d_tgt.p, tgt, size_t(m) * 3 * sizeof(S), kind, s));
   if (n > 0) MOPT_HIP_TRY(hipMemcpyAsync(d_src.p, src, size_t(n) * 3 * sizeof(S), kind, s));
   double lo[3], hi[3];
-  MOPT_HIP_TRY(mopt::icpBoundingBox<S>(d_tgt.as<S>(), m, lo, hi, s));
-  // Cell edge: a hair above the search radius over `reach`, so that the (2 reach + 1)^3 cells around
-  // a query hold every target within the radius.  reach = 1 while that leaves about one target per
-  // cell; where the radius spans many targets the cells are made finer (up to 8 to the radius, and
-  // never more than ~64 M cells: a 256 MB offset table): the search's first round looks at 2 x 2 x 2 cells whatever the
-  // radius, and what it costs goes with the targets in them.  Enlarged instead when even cells of
-  // the radius's size would be more than that.
+  MOPT_HIP_TRY(mopt::cloudBoundingBox<S>(d_tgt.as<S>(), m, lo, hi, s));
+  // The resolution (cell_lattice.hpp has the rules): `reach` cells to the search radius, first by the
+  // box's volume, then by the cells the targets occupy.
   // 2^26 cells (a 256 MB offset table at most) since round 5: a scanned surface fills a thin sheet of
   // its bounding box, and with 2^24 a million-point scan searched within 4 point spacings stayed at one
   // cell to the radius, ~12 targets per occupied cell — whole ICP solves 1 M x 1 M, radius 2 / 4 / 8
   // spacings: 1.29 / 2.16 / 1.90 ms -> 1.21 / 1.30 / 1.46 (profiles/r5_icp_cells_cap.txt; 2^28 gains
   // nothing more: finer cells speed the first round up and slow the second down)
-  static const int cells_log2 = envInt("MOPT_ICP_MAX_CELLS_LOG2", 26);  // (measurements: 20 ... 28)
-  const double kMostCells = double(1ll << (cells_log2 < 20 ? 20 : cells_log2 > 28 ? 28 : cells_log2));
-  auto cellsAt = [&](double edge) {
-    double cells = 1.0;
-    for (int a = 0; a < 3; ++a) cells *= std::floor((hi[a] - lo[a]) / edge) + 1.0;
-    return cells;
-  };
-  const double radius_cell = max_distance * 1.001;
-  auto mostReach = [&](int wanted) {  // the largest reach <= wanted the cell budget allows
-    while (wanted > 1 && cellsAt(radius_cell / wanted) > kMostCells) --wanted;
-    return wanted;
-  };
-  int reach = 1;
+  static const int cells_log2 = envInt("MOPT_ICP_MAX_CELLS_LOG2", mopt::kMostCellsLog2);
   static const int forced_reach = envInt("MOPT_ICP_REACH", 0);  // tests and measurements
-  // (a box thinner than a cell along some axis — a wall, a line, coincident points — says nothing
-  // about the targets per cell by its volume: there the resolution comes from the occupied cells
-  // below alone)
-  bool thin_box = false;
-  for (int a = 0; a < 3; ++a) thin_box = thin_box || !(hi[a] - lo[a] >= radius_cell);
-  if (forced_reach > 0) {
-    reach = mostReach(forced_reach > 8 ? 8 : forced_reach);
-  } else if (!thin_box) {
-    while (reach < 8 && double(m) > 1.5 * cellsAt(radius_cell / reach) && mostReach(reach + 1) > reach)
-      ++reach;
-  }
+  const mopt::SearchBox box(lo, hi, max_distance, mopt::searchCellCap(cells_log2));
+  int reach = box.firstReach(m, forced_reach);
   out_matcher = std::move(mt);  // from here on the caller frees the matcher's device arrays
   IcpMatcher &g = *out_matcher;
   MOPT_HIP_TRY(d_perm_t.alloc(size_t(m) * sizeof(int)));
-  // The box's volume says little about how the targets fill it (a scanned surface occupies a thin
-  // sheet of the cells): after the first binning the cells that hold anything are counted, and while
-  // they hold more than three targets each on average the grid is made finer and the targets are
-  // binned again (at most twice more; a binning is ~0.25 ms per million).  Finer cells that do not
-  // thin the targets out (coincident points; fewer than 1.5 times fewer per occupied cell) only add
-  // empty rows to every search: the grid then goes back to the resolution before, and stays.
+  // the targets binned at `reach`, and again while refineReach asks for another resolution
   int reach_before = 0;
   double per_cell_before = 0.0;
   bool settled = false;
   for (int attempt = 0;; ++attempt) {
-    double cell = radius_cell / reach;
-    while (cellsAt(cell) > kMostCells) cell *= 1.26;  // (only ever with reach == 1)
     g.reach = reach;
-    g.cell = cell;
-    long long ncells = 1;
-    for (int a = 0; a < 3; ++a) {
-      g.origin[a] = lo[a];
-      g.dims[a] = int(std::floor((hi[a] - lo[a]) / cell)) + 1;
-      ncells *= g.dims[a];
-    }
+    g.lattice = box.latticeAt(reach);
+    const long long ncells = g.lattice.cells();
     if (g.d_cell_start) deviceRelease(g.d_cell_start);
     g.d_cell_start = nullptr;
     MOPT_HIP_TRY(deviceAlloc(reinterpret_cast<void **>(&g.d_cell_start), size_t(ncells + 1) * sizeof(int)));
-    MOPT_HIP_TRY(mopt::icpSortByCell<S>(d_tgt.as<S>(), m, g.origin, g.cell, g.dims, d_perm_t.as<int>(),
-                                        g.d_cell_start, s));
-    if (settled || forced_reach > 0 || m == 0 || attempt == 3) break;
-    if (reach == 8 && reach_before == 0) break;  // by the volume rule, nothing finer to try
+    mopt::CellOrder targets;
+    targets.d_perm = d_perm_t.as<int>();
+    targets.d_cell_start = g.d_cell_start;
+    MOPT_HIP_TRY(mopt::sortByCell<S>(d_tgt.as<S>(), m, g.lattice, targets, s));
+    if (settled || !mopt::refinementPossible(reach, reach_before, forced_reach, m)) break;
     long long occupied = 0;
-    MOPT_HIP_TRY(mopt::icpCountOccupiedCells(g.d_cell_start, ncells, &occupied, s));
+    MOPT_HIP_TRY(mopt::countOccupiedCells(g.d_cell_start, ncells, &occupied, s));
     const double per_cell = double(m) / double(occupied > 0 ? occupied : 1);
-    if (reach_before > 0 && per_cell * 1.5 > per_cell_before) {
-      reach = reach_before;
+    const mopt::Refinement next = mopt::refineReach(reach, reach_before, per_cell_before, attempt, per_cell);
+    if (next.what == mopt::Refinement::kStop) break;
+    if (next.what == mopt::Refinement::kStepBack) {
+      reach = next.reach;
       settled = true;
       continue;
     }
-    if (per_cell <= 3.0 || attempt == 2) break;
-    const int wanted = int(std::ceil(reach * std::sqrt(per_cell / 1.5)));
-    const int finer = mostReach(std::min(8, std::max(reach + 1, wanted)));
+    const int finer = box.mostReach(next.reach);
     if (finer <= reach) break;
     reach_before = reach;
     per_cell_before = per_cell;
@@ -119,24 +84,25 @@ int buildIcpGrid(const S *src, long long n, const S *tgt, long long m, double ma
   constexpr long long kTile = mopt::TileShape<S>::kPoints;
   if (m > 0) {
     MOPT_HIP_TRY(deviceAlloc(&g.d_sorted, size_t(m) * 4 * sizeof(S)));
-    MOPT_HIP_TRY(mopt::icpGatherPoints<S>(d_tgt.as<S>(), d_perm_t.as<int>(), m,
-                                          static_cast<S *>(g.d_sorted), true, s));
+    MOPT_HIP_TRY(mopt::gatherByOrder<S>(d_tgt.as<S>(), d_perm_t.as<int>(), m, static_cast<S *>(g.d_sorted),
+                                        true, s));
   }
   // the sources in the cell order of their un-warped position; those with a NaN or infinite
   // coordinate sort behind the others and are left out of the cost (they can have no target, and
   // their arithmetic would turn every sum into NaN): the cost holds the first `kept` of the order
   MOPT_HIP_TRY(d_perm_s.alloc(size_t(n) * sizeof(int)));
-  long long parked = 0;
-  MOPT_HIP_TRY(mopt::icpSortByCell<S>(d_src.as<S>(), n, g.origin, g.cell, g.dims, d_perm_s.as<int>(),
-                                      nullptr, s, &parked));
-  const long long kept = n - parked;
+  mopt::CellOrder sources;
+  sources.d_perm = d_perm_s.as<int>();
+  sources.park_non_finite = true;
+  MOPT_HIP_TRY(mopt::sortByCell<S>(d_src.as<S>(), n, g.lattice, sources, s));
+  const long long kept = n - sources.parked;
   g.num_sources = n;
   g.num_waves = (kept + kTile - 1) / kTile * kTile / 64;
   MOPT_HIP_TRY(deviceAlloc(reinterpret_cast<void **>(&g.d_matched),
                            size_t(g.num_waves > 0 ? g.num_waves : 1) * sizeof(unsigned int)));
   MOPT_HIP_TRY(d_src_sorted.alloc(size_t(kept) * 3 * sizeof(S)));
-  MOPT_HIP_TRY(mopt::icpGatherPoints<S>(d_src.as<S>(), d_perm_s.as<int>(), kept, d_src_sorted.as<S>(),
-                                        false, s));
+  MOPT_HIP_TRY(mopt::gatherByOrder<S>(d_src.as<S>(), d_perm_s.as<int>(), kept, d_src_sorted.as<S>(), false,
+                                      s));
   MOPT_HIP_TRY(hipStreamSynchronize(s));
   g.d_order = d_perm_s.as<int>();  // the matcher keeps the order (its first `kept` entries) on the device
   d_perm_s.p = nullptr;
@@ -157,11 +123,11 @@ void fillIcpArgs(const mopt_cost *c, mopt::IcpMatchArgs<S> &a) {
   a.sorted = static_cast<const S *>(mt.d_sorted);
   a.cell_start = mt.d_cell_start;
   for (int k = 0; k < 3; ++k) {
-    a.origin[k] = S(mt.origin[k]);
-    a.dims[k] = mt.dims[k];
+    a.origin[k] = S(mt.lattice.origin[k]);
+    a.dims[k] = mt.lattice.dims[k];
   }
-  a.inv_cell = S(1.0 / mt.cell);
-  a.cell = S(mt.cell);
+  a.inv_cell = S(1.0 / mt.lattice.edge);
+  a.cell = S(mt.lattice.edge);
   a.reach = mt.reach;
   a.max_dist2 = S(mt.max_dist * mt.max_dist);
   for (int k = 0; k < 12; ++k) a.T[k] = S(k % 5 == 0 ? 1 : 0);
@@ -225,11 +191,7 @@ int mopt_icp_create_from(mopt_cost **out, int device, int scalar_bytes, const vo
     return fail(MOPT_ERR_INVALID_ARGUMENT, "scalar_bytes must be 4 (float) or 8 (double)");
   if (flags & ~unsigned(MOPT_INPUT_DEVICE))
     return fail(MOPT_ERR_INVALID_ARGUMENT, "unknown flag bits (MOPT_INPUT_HOST or MOPT_INPUT_DEVICE)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(MOPT_ERR_NO_DEVICE, "no HIP device is visible to this process");
-  if (device < 0 || device >= ndev) return fail(MOPT_ERR_INVALID_ARGUMENT, "device index out of range");
-  MOPT_HIP_TRY(hipSetDevice(device));
+  if (const int rc = selectDevice(device)) return rc;
   std::unique_ptr<IcpMatcher> matcher;
   auto freeMatcher = [&]() {
     if (!matcher) return;
@@ -285,11 +247,11 @@ int mopt_icp_update(mopt_cost *c, const void *x, int64_t *num_matched) {
 int mopt_icp_grid(const mopt_cost *c, double *cell_edge, int *reach, int dims[3], double origin[3]) {
   if (!c || !c->matcher) return fail(MOPT_ERR_INVALID_ARGUMENT, "not an ICP cost");
   const IcpMatcher &mt = *c->matcher;
-  if (cell_edge) *cell_edge = mt.cell;
+  if (cell_edge) *cell_edge = mt.lattice.edge;
   if (reach) *reach = mt.reach;
   for (int a = 0; a < 3; ++a) {
-    if (dims) dims[a] = mt.dims[a];
-    if (origin) origin[a] = mt.origin[a];
+    if (dims) dims[a] = mt.lattice.dims[a];
+    if (origin) origin[a] = mt.lattice.origin[a];
   }
   return MOPT_OK;
 }

@@ -1,4 +1,4 @@
-// gfx950 kernels of the correspondence search (ICP update step) over the grid icp_grid.hip builds,
+// gfx950 kernels of the correspondence search (ICP update step) over the grid built with cell_order.hip,
 // driven by icp.cpp: the search itself, the gather of the targets it found and the count of matched
 // sources handed to the host.
 #include "sweep_device.hpp"

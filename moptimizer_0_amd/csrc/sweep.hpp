@@ -1,10 +1,12 @@
 // Internal interface between the host units of the library (sweep_launch.cpp, resident.cpp, cost.cpp,
 // icp.cpp, lm.cpp, batch.cpp) and the gfx950 kernels (sweep_kernels.hip, fd_kernels.hip, finalize_kernels.hip,
-// icp_match.hip, layout_kernels.hip, icp_grid.hip, cloud_voxel.hip, cloud_normals.hip).
+// icp_match.hip, layout_kernels.hip, cloud_voxel.hip, cloud_normals.hip).  The cell binning under the search
+// and the cloud filters (cell_order.hip) has its own header, cell_order.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include "aql.hpp"
+#include "cell_lattice.hpp"  // CellLattice: the lattice a search and the normals walk
 #include "dispatch.hpp"
 #include "sweep_choice.hpp"  // forwardStepThreshold: one rule for the blocking calls and the step kernel
 
@@ -508,38 +510,12 @@ template <typename S>
 hipError_t launchGatherTargets(const S *tiles, long long count, const int *order /* or NULL */,
                                S *out_xyz, hipStream_t stream);
 
-// Grid construction for the search (icp_grid.hip).  All pointers are device memory.
-//   icpBoundingBox   min / max of m packed points (synchronises the stream)
-//   icpSortByCell    d_perm[k] = original index of the k-th point in (cell id, original index)
-//                    order; d_cell_start (optional) [cells + 1] offsets into that order
-//                    (synchronises the stream)
-//   icpGatherPoints  out[k] = xyz[d_perm[k]], packed (3) or padded to 4 scalars
-template <typename S>
-hipError_t icpBoundingBox(const S *d_xyz, long long m, double lo[3], double hi[3],
-                          hipStream_t stream,
-                          bool whole_points = false);  // true: a point with any non-finite coordinate
-                                                       // shapes no axis of the box
-template <typename S>
-hipError_t icpSortByCell(const S *d_xyz, long long m, const double origin[3], double cell,
-                         const int dims[3], int *d_perm, int *d_cell_start, hipStream_t stream,
-                         long long *num_parked = nullptr,  // non-NULL: points with a non-finite
-                                                            // coordinate sort last and are counted
-                         unsigned int *d_sorted_keys = nullptr);  // non-NULL: receives the m sorted keys
-// in-place exclusive scan of `length` counters with the sort's scan kernels (synchronises the stream)
-hipError_t icpExclusiveScan(unsigned int *d_data, long long length, hipStream_t stream);
-// cells of the grid that hold at least one point (synchronises the stream)
-hipError_t icpCountOccupiedCells(const int *d_cell_start, long long ncells, long long *occupied,
-                                 hipStream_t stream);
-template <typename S>
-hipError_t icpGatherPoints(const S *d_xyz, const int *d_perm, long long m, S *d_out, bool padded,
-                           hipStream_t stream);
-
 // Voxel-grid downsampling (cloud_voxel.hip; cloud.cpp is its host side).  All pointers are device memory.
 //   launchVoxelHeadFlags   d_flags[k] = 1 where sorted key k differs from key k - 1 (k = 0: 1), and
-//                          d_flags[kept] = 0: kept + 1 entries, so that icpExclusiveScan leaves the
+//                          d_flags[kept] = 0: kept + 1 entries, so that exclusiveScan leaves the
 //                          voxels before every position and, in the last entry, their number
 //   launchVoxelCentroids   one mean per voxel, in ascending key order, from the sorted order of
-//                          icpSortByCell (its first `kept` entries), those scanned flags and
+//                          sortByCell (its first `kept` entries), those scanned flags and
 //                          voxelCarryBytes(kept) of scratch; d_out_counts may be NULL
 hipError_t launchVoxelHeadFlags(const unsigned int *d_sorted_keys, long long kept,
                                 unsigned int *d_flags, hipStream_t stream);
@@ -550,16 +526,17 @@ hipError_t launchVoxelCentroids(const S *d_xyz, const int *d_perm, const unsigne
                                 int32_t *d_out_counts, void *d_carry, hipStream_t stream);
 
 // Radius-neighbourhood PCA normals (cloud_normals.hip; cloud.cpp is its host side).  All
-// pointers are device memory.  The cloud arrives sorted by icpSortByCell over a lattice whose cell edge
+// pointers are device memory.  The cloud arrives sorted by sortByCell over `lattice`, whose cell edge
 // is >= radius: d_perm and d_sorted_keys (`count` entries, the `kept` points with finite coordinates
 // first), d_cell_start (cells + 1 offsets into that order) and d_cell_xyz, the first `kept` points
 // gathered in that order, padded to 4 scalars.  Rows d_perm[k] of the outputs are written for every
 // k < count (NaN and 0 from `kept` on); d_curvature and d_counts may be NULL.
 template <typename S>
 hipError_t launchCloudNormals(const S *d_cell_xyz, const int *d_perm, const unsigned int *d_sorted_keys,
-                              const int *d_cell_start, long long count, long long kept, const int dims[3],
-                              double radius, int min_neighbors, const double viewpoint[3], S *d_normals,
-                              S *d_curvature, int32_t *d_counts, hipStream_t stream);
+                              const int *d_cell_start, long long count, long long kept,
+                              const CellLattice &lattice, double radius, int min_neighbors,
+                              const double viewpoint[3], S *d_normals, S *d_curvature, int32_t *d_counts,
+                              hipStream_t stream);
 
 // sum of the search's per-wave matched counts -> mapped host memory (as one double) + flag
 hipError_t launchPublishCounter(const unsigned int *d_wave_counts, long long num_waves,

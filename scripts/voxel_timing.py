@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Device time of mopt_cloud_voxel_downsample per stage (events on the call's stream:
 mopt_cloud_voxel_profile), beside two yardsticks: the same thinning in numpy on the host (np.unique +
-np.add.reduceat) and the call's own sort stage (one icpSortByCell at that size).
+np.add.reduceat) and the call's own sort stage (one sortByCell at that size).
 
   python scripts/voxel_timing.py --out profiles/voxel_timing.json [--sizes 1000000,10000000] [--reps 5]
 

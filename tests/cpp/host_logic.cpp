@@ -2,7 +2,7 @@
 // status / error behaviour (levenberg_marquadt_dyn.cpp:34-119, optimizer.h:26-54), the pivoted
 // LDL^T it solves with, the dense matrix subset, SO(3) exp / log, loss weights, the logger and
 // the exception type; and the library's host-only headers (csrc/dispatch.hpp, csrc/sweep_choice.hpp: the
-// rules that choose a sweep).  Costs here are tiny closed-form CostFunctionBase subclasses written for
+// rules that choose a sweep, csrc/cell_lattice.hpp: the rules that choose a lattice of cells).  Costs here are tiny closed-form CostFunctionBase subclasses written for
 // the test; nothing from oracle/ or the device path is involved.
 #include <cmath>
 #include <cstdio>
@@ -13,6 +13,7 @@
 #include <stdexcept>
 #include <type_traits>
 
+#include "cell_lattice.hpp"
 #include "dispatch.hpp"
 #include "sweep_choice.hpp"
 #include "moptimizer_amd/cost_function_hip.hpp"
@@ -546,10 +547,151 @@ static void sweepChoiceRules() {
   expectTrue("gridFor: no overflow in num_cus * blocks_per_cu", choice::gridFor(1 << 20, 1 << 20, 1000, 4096) == 1000);
 }
 
+// csrc/cell_lattice.hpp: the lattices the voxel filter, the normal estimation and the correspondence
+// search bin on.  Expected values are worked out here by hand from the rules.
+static void cellLatticeRules() {
+  using mopt::CellLattice;
+  // voxelLattice, leaf 0.5: origin = floor(lo / leaf) * leaf = (floor(-2.4), floor(0), floor(0.6)) * 0.5;
+  // dims = floor((hi - origin) / leaf) + 1 = (floor(8.2), floor(0), floor(0.6)) + 1
+  {
+    const double lo[3] = {-1.2, 0.0, 0.3}, hi[3] = {2.6, 0.0, 0.3};
+    double cells = 0.0;
+    const CellLattice g = mopt::voxelLattice(lo, hi, 0.5, cells);
+    expectTrue("voxelLattice: origin (-1.5, 0, 0)", g.origin[0] == -1.5 && g.origin[1] == 0.0 && g.origin[2] == 0.0);
+    expectTrue("voxelLattice: dims (9, 1, 1)", g.dims[0] == 9 && g.dims[1] == 1 && g.dims[2] == 1);
+    expectTrue("voxelLattice: edge is the leaf, 9 cells", g.edge == 0.5 && cells == 9.0 && g.cells() == 9);
+    bool covers = true;
+    for (int a = 0; a < 3; ++a)
+      covers = covers && g.origin[a] <= lo[a] && g.origin[a] + g.dims[a] * g.edge > hi[a];
+    expectTrue("voxelLattice: origin <= lo and origin + dims * leaf > hi on every axis", covers);
+  }
+  // [0, 2000]^3: leaf 1 gives 2001^3 = 8.012e9 cells, over 2^31 - 1; 1290^3 = 2146689000 <= 2147483647 <
+  // 1291^3 = 2151685171, so the smallest leaf that fits has floor(2000 / leaf) = 1289: just above 2000 / 1290
+  {
+    const double lo[3] = {0, 0, 0}, hi[3] = {2000, 2000, 2000};
+    double cells = 0.0;
+    (void)mopt::voxelLattice(lo, hi, 1.0, cells);
+    expectTrue("voxelLattice: 2001^3 cells are counted, and are over the cap",
+               cells == 2001.0 * 2001.0 * 2001.0 && !(cells <= mopt::kMostVoxels));
+    expectTrue("kMostVoxels is 2^31 - 1", mopt::kMostVoxels == 2147483647.0);
+    const double leaf = mopt::smallestLeafThatFits(lo, hi, 1.0);
+    const CellLattice g = mopt::voxelLattice(lo, hi, leaf, cells);
+    expectTrue("smallestLeafThatFits: dims (1290, 1290, 1290)",
+               g.dims[0] == 1290 && g.dims[1] == 1290 && g.dims[2] == 1290 && cells == 2146689000.0);
+    expectNear("smallestLeafThatFits: just above 2000 / 1290", leaf, 2000.0 / 1290.0, 1e-12);
+    (void)mopt::voxelLattice(lo, hi, leaf - 1e-6, cells);
+    expectTrue("smallestLeafThatFits: a leaf 1e-6 smaller takes 1291^3 cells and does not fit",
+               cells == 2151685171.0 && !(cells <= mopt::kMostVoxels));
+    const double lo2[3] = {-1.2, 0.0, 0.3}, hi2[3] = {2.6, 0.0, 0.3};
+    expectTrue("smallestLeafThatFits: a leaf that fits comes back as it is",
+               mopt::smallestLeafThatFits(lo2, hi2, 0.5) == 0.5);
+  }
+  // normalsLattice over [0, 1000]^3, radius 1: edges (1 + 2^-20) x 1, 2, 4 give floor(1000 / edge) + 1 =
+  // 1000, 500, 250 cells an axis; 1000^3 and 500^3 = 1.25e8 exceed 2^26 = 67108864, 250^3 = 15625000 does not
+  {
+    const double lo[3] = {0, 0, 0}, hi[3] = {1000, 1000, 1000};
+    expectTrue("kMostCells is 2^26", mopt::kMostCells == 67108864.0 && mopt::kMostCellsLog2 == 26);
+    const CellLattice g = mopt::normalsLattice(lo, hi, 1.0);
+    expectTrue("normalsLattice: two doublings, edge 4 (1 + 2^-20) exactly", g.edge == 4.0 * (1.0 + 0x1p-20));
+    expectTrue("normalsLattice: dims (250, 250, 250)", g.dims[0] == 250 && g.dims[1] == 250 && g.dims[2] == 250);
+    expectTrue("normalsLattice: anchored at the world origin", g.origin[0] == 0.0 && g.origin[1] == 0.0 && g.origin[2] == 0.0);
+    // radius 10: floor(1000 / 10.0000095) + 1 = 100 an axis, 1e6 cells
+    const CellLattice h = mopt::normalsLattice(lo, hi, 10.0);
+    expectTrue("normalsLattice: radius 10 needs no doubling, edge 10 (1 + 2^-20) > radius",
+               h.edge == 10.0 * (1.0 + 0x1p-20) && h.edge > 10.0);
+    expectTrue("normalsLattice: radius 10, dims (100, 100, 100)", h.dims[0] == 100 && h.dims[1] == 100 && h.dims[2] == 100);
+  }
+  // the search: radius_cell = 1.001 max_distance; a cube of side 100 searched within 1
+  {
+    const double lo[3] = {0, 0, 0}, hi[3] = {100, 100, 100};
+    const mopt::SearchBox box(lo, hi, 1.0, mopt::kMostCells);
+    expectTrue("SearchBox: radius_cell = 1.001 max_distance", box.radius_cell == 1.0 * 1.001);
+    // floor(100 / 1.001) + 1 = 99 + 1 an axis
+    expectTrue("SearchBox: cellsAt(1.001) = 100^3", box.cellsAt(1.001) == 1e6);
+    expectTrue("searchCellCap: 26 is 2^26, clamped to 2^20 ... 2^28",
+               mopt::searchCellCap(26) == mopt::kMostCells && mopt::searchCellCap(3) == 1048576.0 &&
+                   mopt::searchCellCap(31) == 268435456.0);
+    expectTrue("SearchBox: the cube is not thin", !box.thin());
+    expectTrue("firstReach: m = 1e6 is not above 1.5 x 1e6 cells: reach 1", box.firstReach(1000000, 0) == 1);
+    // m = 1e7 > 1.5e6: reach 2, whose edge 0.5005 gives (floor(199.8) + 1)^3 = 8e6 cells; 1e7 < 1.2e7 stops there
+    const int reach = box.firstReach(10000000, 0);
+    expectTrue("firstReach: m = 1e7 gives reach 2", reach > 1 && reach == 2);
+    expectTrue("firstReach: the cells at that reach are within the cap",
+               box.cellsAt(box.radius_cell / reach) == 8e6 && box.cellsAt(box.radius_cell / reach) <= box.most_cells);
+    // forced: 20 is clamped to 8; edge 1.001 / 4 gives 400^3 = 6.4e7 <= 2^26 < 500^3 at reach 5
+    expectTrue("firstReach: forced 20 -> 8 -> 4 under 2^26 cells", box.firstReach(10, 20) == 4);
+    expectTrue("mostReach(8) under 2^26 cells", box.mostReach(8) == 4);
+    // ... and under 2^20 = 1048576 only reach 1 (100^3) fits: 200^3 = 8e6 at reach 2
+    const mopt::SearchBox tight(lo, hi, 1.0, mopt::searchCellCap(20));
+    expectTrue("firstReach: forced 20 -> 8 -> 1 under 2^20 cells", tight.firstReach(10, 20) == 1);
+    expectTrue("firstReach: forced 1 stays, whatever m is", box.firstReach(100000000, 1) == 1);
+    const CellLattice g = box.latticeAt(2);
+    expectTrue("latticeAt(2): edge radius_cell / 2, dims 200^3, anchored at lo",
+               g.edge == box.radius_cell / 2 && g.dims[0] == 200 && g.dims[1] == 200 && g.dims[2] == 200 &&
+                   g.origin[0] == 0.0 && g.cells() == 8000000);
+    // a box thinner than radius_cell on one axis: reach 1, whatever m is
+    const double flat_hi[3] = {100, 100, 1.0};
+    const mopt::SearchBox wall(lo, flat_hi, 1.0, mopt::kMostCells);
+    expectTrue("SearchBox: 1.0 < 1.001 on one axis is thin", wall.thin());
+    expectTrue("firstReach: a thin box gives reach 1 for m = 10", wall.firstReach(10, 0) == 1);
+    expectTrue("firstReach: a thin box gives reach 1 for m = 1e9", wall.firstReach(1000000000, 0) == 1);
+    const double exact_hi[3] = {100, 100, 1.0 * 1.001};
+    expectTrue("SearchBox: an extent of exactly radius_cell is not thin",
+               !mopt::SearchBox(lo, exact_hi, 1.0, mopt::kMostCells).thin());
+  }
+  // [0, 1000]^3 searched within 1 under 2^20 = 1048576 cells: 1000^3 at edge 1.001; the edge grows by 1.26
+  // until dims <= 101 (101^3 = 1030301), i.e. edge > 1000 / 101 = 9.90: 1.001 x 1.26^9 = 8.01 (125 an axis)
+  // does not, 1.001 x 1.26^10 = 10.10 (floor(99.05) + 1 = 100 an axis) does
+  {
+    const double lo[3] = {0, 0, 0}, hi[3] = {1000, 1000, 1000};
+    const mopt::SearchBox box(lo, hi, 1.0, mopt::searchCellCap(20));
+    expectTrue("firstReach: 1e9 cells at reach 1 are over the cap, reach stays 1", box.firstReach(5000000, 0) == 1);
+    double edge = 1.0 * 1.001;
+    for (int k = 0; k < 10; ++k) edge *= 1.26;
+    const CellLattice g = box.latticeAt(1);
+    expectTrue("latticeAt(1): ten growths by 1.26", g.edge == edge);
+    expectTrue("latticeAt(1): dims (100, 100, 100) fit 2^20", g.dims[0] == 100 && g.dims[1] == 100 && g.dims[2] == 100 &&
+                                                                 double(g.cells()) <= box.most_cells);
+  }
+  // the refinement by occupied cells
+  {
+    using mopt::Refinement;
+    expectTrue("refinementPossible: a first binning of some targets", mopt::refinementPossible(1, 0, 0, 1000));
+    expectTrue("refinementPossible: not with a forced reach", !mopt::refinementPossible(1, 0, 2, 1000));
+    expectTrue("refinementPossible: not without targets", !mopt::refinementPossible(1, 0, 0, 0));
+    expectTrue("refinementPossible: not at reach 8 by the volume rule", !mopt::refinementPossible(8, 0, 0, 1000));
+    expectTrue("refinementPossible: at reach 8 after a refinement (it may step back)", mopt::refinementPossible(8, 3, 0, 1000));
+    Refinement r = mopt::refineReach(1, 0, 0.0, 0, 2.9);
+    expectTrue("refineReach: 2.9 targets per occupied cell stop", r.what == Refinement::kStop);
+    r = mopt::refineReach(1, 0, 0.0, 0, 3.0);
+    expectTrue("refineReach: 3 stop too", r.what == Refinement::kStop);
+    r = mopt::refineReach(1, 0, 0.0, 0, 12.0);
+    expectTrue("refineReach: 12 per cell at reach 1 want ceil(sqrt(8)) = 3", r.what == Refinement::kFiner && r.reach == 3);
+    r = mopt::refineReach(2, 0, 0.0, 0, 3.5);  // ceil(2 sqrt(3.5 / 1.5)) = ceil(3.06) = 4
+    expectTrue("refineReach: 3.5 per cell at reach 2 want 4", r.what == Refinement::kFiner && r.reach == 4);
+    r = mopt::refineReach(4, 0, 0.0, 0, 3.1);  // ceil(4 sqrt(3.1 / 1.5)) = ceil(5.75) = 6
+    expectTrue("refineReach: 3.1 per cell at reach 4 want 6", r.what == Refinement::kFiner && r.reach == 6);
+    r = mopt::refineReach(2, 0, 0.0, 0, 600.0);  // ceil(2 sqrt(400)) = 40
+    expectTrue("refineReach: never beyond reach 8", r.what == Refinement::kFiner && r.reach == 8);
+    // second reading: 9 x 1.5 = 13.5 > 12, thinned out by less than 1.5 times
+    r = mopt::refineReach(3, 1, 12.0, 1, 9.0);
+    expectTrue("refineReach: 12 -> 9 per cell steps back to the reach before", r.what == Refinement::kStepBack && r.reach == 1);
+    r = mopt::refineReach(3, 1, 12.0, 1, 2.0);  // 3 <= 12: thinned out; 2 <= 3 stops
+    expectTrue("refineReach: 12 -> 2 per cell stays and stops", r.what == Refinement::kStop);
+    r = mopt::refineReach(3, 1, 12.0, 1, 6.0);  // 9 <= 12; ceil(3 sqrt(4)) = 6
+    expectTrue("refineReach: 12 -> 6 per cell refines once more, to 6", r.what == Refinement::kFiner && r.reach == 6);
+    r = mopt::refineReach(6, 3, 6.0, 2, 3.5);  // 5.25 <= 6: thinned out, but two refinements were made
+    expectTrue("refineReach: never a third refinement", r.what == Refinement::kStop);
+    r = mopt::refineReach(6, 3, 6.0, 2, 5.0);  // 7.5 > 6
+    expectTrue("refineReach: the third binning may still step back", r.what == Refinement::kStepBack && r.reach == 3);
+  }
+}
+
 int main() {
   optimizerStatuses();
   dispatchPrimitives();
   sweepChoiceRules();
+  cellLatticeRules();
   ldlt();
   denseAndSo3();
   lossThresholdRecovery();

@@ -55,6 +55,22 @@ def test_every_point_its_own_voxel_in_ascending_id(hip_lib, dtype):
     assert np.array_equal(out, lattice[order].astype(dtype)) and (counts == 1).all()
 
 
+# The head flags' scan (exclusiveScan, csrc/cell_order.hpp) runs over kept + 1 entries in tiles of 1024, and
+# its middle step has one thread per tile total up to 256 tiles, several totals per thread beyond: kept + 1
+# on both sides of one tile (1024) and of 256 tiles (262 144).  The dims multiply to `kept`.
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dims", [(3, 11, 31), (8, 8, 16), (57, 63, 73), (64, 64, 64)])
+def test_every_point_its_own_voxel_across_the_scan_regimes(hip_lib, dtype, dims):
+    kept = dims[0] * dims[1] * dims[2]
+    assert kept + 1 in (1024, 1025, 262144, 262145)
+    i, j, k = np.meshgrid(np.arange(dims[0]), np.arange(dims[1]), np.arange(dims[2]), indexing="ij")
+    lattice = (np.column_stack([i.ravel(), j.ravel(), k.ravel()]) + 0.5) * 0.5  # exact in fp32 too
+    pts = lattice[np.random.default_rng(kept).permutation(kept)].astype(dtype)
+    out, counts = _check(hip_lib, pts, 0.5)
+    order = np.lexsort((lattice[:, 0], lattice[:, 1], lattice[:, 2]))  # x fastest, then y, then z
+    assert np.array_equal(out, lattice[order].astype(dtype)) and (counts == 1).all()
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_giant_voxels_on_both_edges_of_the_tiles(hip_lib, dtype):
     rng = np.random.default_rng(8)
